@@ -2,6 +2,7 @@
 """bench.py -- headline benchmark of the FFT executor on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2c|r2c|mixed|2d|dct2|dct2-2d|slab2d]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one fftw_execute of the whole batch of synthetic input that is
 already resident in HBM.  At N=1 the default workload is BASELINE.json
@@ -9,16 +10,23 @@ configs[1]: 1-D complex double N = 2^20, howmany = 4096 (fftw_plan_many_dft),
 forward, out of place.  The metric is the reference's own
 (fftw/libbench2/mflops.c:21-28): GFLOPS = 5 N log2 N * howmany / t.
 
+A plain run sets up, runs W warm-ups and K timed steps and prints the line;
+nothing else.  `--full` adds what takes runs of its own: the roofline (one
+profiled execution per workload), the other BASELINE workloads as
+`config.legs` and the CPU baseline.  `--dump-outputs DIR` writes what the
+last timed step computed to DIR/*.npy (see dump_outputs); the inputs are
+seeded, so two builds can be compared output for output.
+
 With --gpus N > 1 the driver launches one process per GPU
 (torch.distributed.run); whole batch elements are sharded across ranks, every
 rank transforms the same per-GPU batch (weak scaling) and nothing is exchanged
 inside the timed region.  `--gather` adds the RCCL all-gather of the outputs
 (reported separately: it is xGMI-bound).
 
-Rank 0 prints ONE JSON line.  It carries `roofline` for the dominant kernel
-(HIP events around every launch, on the stream the kernels run on) and, at
-N=1, `cpu_baseline`: the CPU oracle timed on one host core on a bounded sample
-of the same workload.
+Rank 0 prints ONE JSON line.  With --full it carries `roofline` for the dominant
+kernel (HIP events around every launch, on the stream the kernels run on) and,
+at N=1, `cpu_baseline`: the CPU oracle timed on one host core on a bounded
+sample of the same workload.
 """
 import argparse
 import ctypes as C
@@ -100,6 +108,40 @@ def pmc_traffic(name, alg_bytes_per_step):
     return w["traffic_over_algorithmic"] * alg_bytes_per_step, (
         "profiles/r03_traffic.json (static: rocprofv3 --pmc passes of the same command; %.3f x the algorithmic bytes)"
         % w["traffic_over_algorithmic"])
+
+
+DUMP_BYTES = 60 << 20     # all files of one --dump-outputs call together (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write the device tensors `arrays` (name -> tensor the timed path handed to its caller) to
+    out_dir/<name>*.npy as float64, complex values as a trailing axis of 2 (re, im).  An array that
+    fits its share of DUMP_BYTES is written whole as <name>.npy; a larger one as <name>_first.npy
+    (its first transform, cut to half the share) and <name>_sample.npy: the elements at the flat
+    indices np.unique(default_rng(0).integers(0, numel, k)) with k filling the rest of the share,
+    so the sample covers every chunk of the batch and is the same from run to run."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        item = 16 if t.is_complex() else 8
+
+        def host(v):
+            v = torch.view_as_real(v) if v.is_complex() else v
+            return v.to(torch.float64).cpu().numpy()
+        if t.numel() * item <= share:
+            np.save(os.path.join(out_dir, name + ".npy"), host(t))
+            continue
+        first = t.reshape(t.shape[0], -1)[0] if t.dim() > 1 else t
+        first = first[:max(1, share // 2 // item)]
+        np.save(os.path.join(out_dir, name + "_first.npy"), host(first))
+        k = max(1, (share - first.numel() * item) // item)
+        idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), k, dtype=np.int64))
+        flat = t.reshape(-1)
+        np.save(os.path.join(out_dir, name + "_sample.npy"),
+                host(flat[torch.from_numpy(idx).to(flat.device)]))
 
 
 # reference numbers measured by the survey on this container's CPU (BASELINE.md section 2): the
@@ -209,10 +251,12 @@ def cpu_baseline(n, kind, flops_per_transform, target_seconds=8.0, all_cores=Tru
     return out
 
 
-def run_workload(name, batch_override, steps, warmup, torch, fa, dist, world, rank, dev, want_cpu, cpu_seconds=8.0):
+def run_workload(name, batch_override, steps, warmup, torch, fa, dist, world, rank, dev, want_cpu, cpu_seconds=8.0,
+                 want_roofline=False, dump_dir=None):
     """One BASELINE config on this rank's GPU: plan, W warm-ups, K timed executions between
     barriers (wall clock, max over ranks) plus a HIP-event pair around every single step for
-    min / median, the per-launch roofline of the dominant kernel, and the CPU baseline."""
+    min / median; optionally the outputs of the last timed step (`dump_dir`, rank 0), the
+    per-launch roofline of the dominant kernel and the CPU baseline."""
     n, b, kind, flops1, abytes1 = workload(name, batch_override)
     size = 1
     for v in n:
@@ -302,6 +346,8 @@ def run_workload(name, batch_override, steps, warmup, torch, fa, dist, world, ra
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {"out": y})      # before anything executes the plan again (in-place variant)
 
     total_transforms = b * world * steps
     gflops = flops1 * total_transforms / dt / 1e9
@@ -311,9 +357,11 @@ def run_workload(name, batch_override, steps, warmup, torch, fa, dist, world, ra
     # read once + written once, whatever the number of trips the plan makes -- over the timed region of
     # this rank; the dominant kernel's own launches (HIP events around every launch, on the stream the
     # kernel is launched on) are reported beside it under per_launch
-    prof = plan.execute_profiled()
-    torch.cuda.synchronize()
     roof = None
+    prof = None
+    if want_roofline:
+        prof = plan.execute_profiled()
+        torch.cuda.synchronize()
     if prof:
         dom = max(prof, key=lambda t: t[1])
         st, ms, launches = dom
@@ -392,20 +440,26 @@ def run_slab(args, torch, fa, dist, world, rank, dev):
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    # time of the exchanges alone (same buffers, same splits)
-    ex = [p for k, p in plan.stages if k == "a2a"]
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        for e in ex:
-            e.run()
-    barrier()
-    dte = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": y[:ln0 * n1]})     # this rank's rows of the result (normal out)
+    exchange = None
+    if args.full:
+        # time of the exchanges alone (same buffers, same splits)
+        ex = [p for k, p in plan.stages if k == "a2a"]
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            for e in ex:
+                e.run()
+        barrier()
+        dte = time.perf_counter() - t0
+        sent = sum(sum(e.send_counts) - e.send_counts[rank] for e in ex) * 16
+        exchange = {"ms_per_step": dte / args.steps * 1e3, "bytes_sent_per_rank_per_step": sent,
+                    "GBs_per_rank": sent * args.steps / dte / 1e9 if dte > 0 else None}
     size = n0 * n1
     flops = 5.0 * size * math.log2(size)
     if rank == 0:
-        sent = sum(sum(e.send_counts) - e.send_counts[rank] for e in ex) * 16
-        print(json.dumps({
+        out = {
             "metric": "GFLOPS (5N*log2N), one 2D complex double transform %dx%d in slabs over the GPUs" % (n0, n1),
             "value": flops * args.steps / dt / 1e9, "unit": "GFLOPS", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -413,9 +467,10 @@ def run_slab(args, torch, fa, dist, world, rank, dev):
             "config": {"workload": "slab2d %dx%d c2c forward, normal in / normal out" % (n0, n1),
                        "local_plans": plan.num_local_plans(), "exchanges": plan.num_exchanges(),
                        "parallelism": "slab x%d" % world},
-            "exchange": {"ms_per_step": dte / args.steps * 1e3, "bytes_sent_per_rank_per_step": sent,
-                         "GBs_per_rank": sent * args.steps / dte / 1e9 if dte > 0 else None},
-        }))
+        }
+        if exchange:
+            out["exchange"] = exchange
+        print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
 
@@ -491,9 +546,16 @@ def main():
     ap.add_argument("--workload", default="c2c")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU howmany override")
     ap.add_argument("--gather", action="store_true", help="also time the RCCL all-gather of outputs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline workload only (no backward / r2c / c2r / mixed / 2d legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the other BASELINE workloads (legs) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="with --full: headline workload only (no backward / r2c / c2r / mixed / 2d legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.
@@ -544,7 +606,8 @@ def main():
         return run_slab(args, torch, fa, dist, world, rank, dev)
 
     res = run_workload(args.workload, args.batch, args.steps, args.warmup, torch, fa, dist, world, rank, dev,
-                       want_cpu=(world == 1 and rank == 0 and not args.no_cpu_baseline))
+                       want_cpu=(args.full and world == 1 and rank == 0 and not args.no_cpu_baseline),
+                       want_roofline=args.full, dump_dir=args.dump_outputs)
     y = res.pop("_y")
     n, b, kind, size, free = res["n"], res["howmany"], res["kind"], res["size"], res["free"]
 
@@ -569,7 +632,7 @@ def main():
 
     # ---- the other BASELINE configs, one GPU, same measurement (reported as legs, never as `value`)
     legs = []
-    if world == 1 and args.workload == "c2c" and not args.no_legs and not args.batch:
+    if args.full and world == 1 and args.workload == "c2c" and not args.no_legs and not args.batch:
         base_cfg = {"c2c-bwd-inplace": "configs[1], backward + in-place variant (SURVEY.md 8d row 2)",
                     "r2c": "configs[2]", "c2r": "configs[2], c2r of the r2c result (SURVEY.md 8d row 3)",
                     "mixed": "configs[3] (sub-batch 256 of 2048: 504 GB per array do not fit one GPU)",
@@ -579,7 +642,8 @@ def main():
             # the backward / c2r variants run the same CPU code path as their forward twins: one CPU baseline each pair
             twin = {"c2c-bwd-inplace": "c2c", "c2r": "r2c"}.get(name)
             lr = run_workload(name, 0, max(3, args.steps // 2), 1, torch, fa, None, 1, 0, dev,
-                              want_cpu=not args.no_cpu_baseline and twin is None, cpu_seconds=4.0)
+                              want_cpu=not args.no_cpu_baseline and twin is None, cpu_seconds=4.0,
+                              want_roofline=True)
             lr.pop("_y")
             torch.cuda.empty_cache()
             if twin is None:
@@ -615,8 +679,9 @@ def main():
                 kind, "x".join(str(v) for v in n), b, res["variant"]),
                 "algorithmic_GBs": res["alg_gbs"], "parallelism": "batch-sharded x%d" % world,
                 "plan": res["plan"]},
-            "roofline": res["roofline"],
         }
+        if args.full:
+            out["roofline"] = res["roofline"]
         if legs:
             out["config"]["legs"] = legs
         if gather:

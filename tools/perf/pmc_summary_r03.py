@@ -2,7 +2,7 @@
 
     python tools/perf/pmc_summary_r03.py <prof_dir> <out.json>
 
-One FETCH_SIZE pass and one WRITE_SIZE pass per workload, each over `python3 bench.py --workload W --steps 1
+One FETCH_SIZE pass and one WRITE_SIZE pass per workload, each over `python3 bench.py --full --workload W --steps 1
 --warmup 1 --no-legs --no-cpu-baseline` = 3 executions of the plan (warm-up, timed step, per-launch profiled
 execution).  FETCH_SIZE / WRITE_SIZE are in KB of 1024 B.  gfx950 correction (MI355X_MICROARCH.md, HBM section):
 FETCH_SIZE tallies 128-byte requests at 64 B, so read bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE is exact for

@@ -9,7 +9,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 for W in ${WORKLOADS:-c2c r2c c2r mixed 2d}; do
   echo "== $W: kernel stats" 
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 bench.py --workload $W --steps 5 --warmup 2 --no-legs --no-cpu-baseline > $O/r03_bench_${W}_under_rocprof.json 2> $O/stats_$W.err || { echo "stats run failed for $W"; tail -5 $O/stats_$W.err; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- python3 bench.py --full --workload $W --steps 5 --warmup 2 --no-legs --no-cpu-baseline > $O/r03_bench_${W}_under_rocprof.json 2> $O/stats_$W.err || { echo "stats run failed for $W"; tail -5 $O/stats_$W.err; }
   S=$(find $O/stats_$W -name "*kernel_stats.csv" | head -1)
   python3 - "$S" $O/r03_${W}_kernel_stats.csv <<'PY'
 import csv, sys
@@ -26,7 +26,7 @@ PY
   if [ "$W" != "c2r" ]; then
     for C in FETCH_SIZE WRITE_SIZE; do
       echo "== $W: pmc $C"
-      rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/${C}_$W -- python3 bench.py --workload $W --steps 1 --warmup 1 --no-legs --no-cpu-baseline > $O/pmc_${C}_$W.json 2> $O/pmc_${C}_$W.err || { echo "pmc run failed"; tail -5 $O/pmc_${C}_$W.err; }
+      rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/${C}_$W -- python3 bench.py --full --workload $W --steps 1 --warmup 1 --no-legs --no-cpu-baseline > $O/pmc_${C}_$W.json 2> $O/pmc_${C}_$W.err || { echo "pmc run failed"; tail -5 $O/pmc_${C}_$W.err; }
     done
   fi
   rm -rf $O/stats_$W/*/*_agent_info.csv
