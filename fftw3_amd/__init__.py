@@ -155,6 +155,10 @@ _sig("fftw_amd_slab_sync", None, _vp)
 _sig("fftw_amd_slab_num_devices", C.c_int, _vp)
 _sig("fftw_amd_slab_local_plan", _vp, _vp, C.c_int, C.c_int)
 _sig("fftw_amd_destroy_slab_plan", None, _vp)
+_sig("fftw_amd_slab_local_size_1d", C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_uint,
+     C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
+_sig("fftw_amd_slab_split_1d", C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
+_sig("fftw_amd_slab_plan_dft_1d", _vp, C.c_longlong, C.c_int, C.POINTER(C.c_int), _vpp, _vpp, C.c_int, C.c_uint)
 _sig("fftw_amd_sharded_gather_ops", C.c_int, _vp, _vpp, C.POINTER(C.c_longlong), C.c_int)
 _sig("fftw_amd_rccl_probe", C.c_int)
 _sig("fftw_amd_plan_workspace_device", C.c_int, _vp)
@@ -700,3 +704,37 @@ class SlabPlanC(object):
             self.destroy()
         except Exception:
             pass
+
+
+# ---- one long 1-D transform over the GPUs of this process (fftw3_amd/csrc/slab1d.c)
+
+SLAB_SCRAMBLED_IN = 1 << 27
+SLAB_SCRAMBLED_OUT = 1 << 28
+
+
+def slab_local_size_1d(n, ndev, g, sign, flags=0):
+    """fftw_amd_slab_local_size_1d: (elements, local_ni, local_i_start, local_no, local_o_start) of device g;
+    elements is -1 when no plan exists for (n, ndev)"""
+    v = [C.c_longlong(0) for _ in range(4)]
+    tot = lib.fftw_amd_slab_local_size_1d(n, ndev, g, sign, flags, *[C.byref(x) for x in v])
+    return (tot,) + tuple(x.value for x in v)
+
+
+def slab_split_1d(n, ndev, sign):
+    """fftw_amd_slab_split_1d: the planner's (n0, n1), None when there is no split"""
+    n0, n1 = C.c_longlong(0), C.c_longlong(0)
+    if lib.fftw_amd_slab_split_1d(n, ndev, sign, C.byref(n0), C.byref(n1)):
+        return None
+    return n0.value, n1.value
+
+
+class SlabPlan1dC(SlabPlanC):
+    """fftw_amd_slab_plan_dft_1d: one 1-D complex transform of length n cut over several devices (ins[g] / outs[g]
+    hold n / len(devs) elements each; layouts in include/fftw3_amd.h)"""
+
+    def __init__(self, n, devs, ins, outs, sign, flags=ESTIMATE):
+        dv = (C.c_int * len(devs))(*devs)
+        self.handle = lib.fftw_amd_slab_plan_dft_1d(n, len(devs), dv, _ptrs(ins), _ptrs(outs), sign, flags)
+        if not self.handle:
+            raise ValueError("1-d slab planner returned NULL (invalid or unsupported problem)")
+        self._keep = (ins, outs)

@@ -50,6 +50,14 @@ void  fa_hip_memcpy_peer(void *dst, int dst_dev, const void *src, int src_dev, s
 /* 2-D device-to-device copy (rows of `width` bytes, `height` of them), source and destination possibly on different
    devices with peer access; asynchronous on `stream` (a stream of the current device) */
 void  fa_hip_memcpy2d_peer(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, void *stream);
+size_t fa_hip_max_pitch(int dev);               /* largest pitch (bytes) of a 2-D copy on dev, 0: unknown */
+
+/* Distributed 1-D transform (slab1d.c, kernels_slab.hip): in place, element (k0, c) of the rows x width block at p
+   (complex values, rows row_stride apart) times w^(k0 (c0 + c)), w = exp(sign 2 pi i / n), from the two-level table
+   lo[m & (2^shift - 1)] * hi[m >> shift] of (cos, sin)(2 pi m / n) (device pointers).  Every exponent must stay
+   below n.  Returns 0 when launched on stream, 1 on invalid arguments. */
+int   fa_hip_slab_twiddle(double *p, long long rows, long long width, long long row_stride, long long c0,
+                          long long n, int sign, const void *lo, const void *hi, int shift, void *stream);
 
 /* Launch one step.  bufs[i] is the device base pointer of buffer id i, tables[i]
    the device pointer of table id i.  (chunk_start, chunk_n) select the slice

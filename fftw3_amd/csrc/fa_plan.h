@@ -174,4 +174,13 @@ fa_cfg fa_default_cfg(void);
 /* api.c */
 struct fftw_plan_s *fa_unaligned_twin(const struct fftw_plan_s *p);
 
+/* slab1d.c: the distributed 1-D transform; slab.c wraps it in an fftw_amd_slab_plan and dispatches to it */
+#define FA_SLAB_MAXDEV 32
+struct fa_slab1d;
+void fa_slab1d_execute(struct fa_slab1d *d);
+void fa_slab1d_sync(struct fa_slab1d *d);
+void fa_slab1d_destroy(struct fa_slab1d *d);
+fftw_plan fa_slab1d_local_plan(const struct fa_slab1d *d, int g, int which);
+struct fftw_amd_slab_plan_s *fa_slab_wrap1d(struct fa_slab1d *d, int ndev);   /* slab.c; NULL: out of memory */
+
 #endif

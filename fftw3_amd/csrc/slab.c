@@ -28,8 +28,6 @@
 #include "fa_plan.h"
 #include "fa_hip.h"
 
-#define FA_SLAB_MAXDEV 32
-
 struct fftw_amd_slab_plan_s {
     int ndev, devs[FA_SLAB_MAXDEV];
     long long n0, n1, inner, R;                       /* rows, split dimension, elements per n1 entry, R = n1 * inner */
@@ -41,6 +39,7 @@ struct fftw_amd_slab_plan_s {
     void *stream[FA_SLAB_MAXDEV];
     void *ev_rows[FA_SLAB_MAXDEV], *ev_x1[FA_SLAB_MAXDEV], *ev_cols[FA_SLAB_MAXDEV], *ev_done[FA_SLAB_MAXDEV];
     int ran;                                           /* ev_done holds the end of a previous execution */
+    struct fa_slab1d *d1;                              /* a 1-D plan (slab1d.c): everything above unused but ndev */
 };
 
 /* block rule of fftw/mpi/block.c:39-50 (default block = ceil(n / P)) */
@@ -68,6 +67,7 @@ long long fftw_amd_slab_local_size(int rank, const long long *n, int ndev, int g
 void fftw_amd_destroy_slab_plan(struct fftw_amd_slab_plan_s *p) {
     int g, cur;
     if (!p) return;
+    if (p->d1) { fa_slab1d_destroy(p->d1); free(p); return; }
     cur = fa_hip_device_count() > 0 ? fa_hip_get_device() : -1;
     for (g = 0; g < p->ndev; ++g) {
         if (cur >= 0) fa_hip_set_device(p->devs[g]);
@@ -164,6 +164,7 @@ fail:
 void fftw_amd_slab_execute(struct fftw_amd_slab_plan_s *p) {
     int g, r, saved;
     if (!p) return;
+    if (p->d1) { fa_slab1d_execute(p->d1); return; }
     if (fa_hip_device_count() <= 0) {
         fprintf(stderr, "fftw3_amd: no HIP device available: a slab plan cannot execute (no CPU fallback)\n");
         abort();
@@ -214,6 +215,7 @@ void fftw_amd_slab_execute(struct fftw_amd_slab_plan_s *p) {
 void fftw_amd_slab_sync(struct fftw_amd_slab_plan_s *p) {
     int g, saved;
     if (!p || fa_hip_device_count() <= 0) return;
+    if (p->d1) { fa_slab1d_sync(p->d1); return; }
     saved = fa_hip_get_device();
     for (g = 0; g < p->ndev; ++g) {
         fa_hip_set_device(p->devs[g]);
@@ -225,5 +227,14 @@ void fftw_amd_slab_sync(struct fftw_amd_slab_plan_s *p) {
 int fftw_amd_slab_num_devices(const fftw_amd_slab_plan p) { return p ? p->ndev : 0; }
 fftw_plan fftw_amd_slab_local_plan(const fftw_amd_slab_plan p, int g, int which) {
     if (!p || g < 0 || g >= p->ndev) return NULL;
+    if (p->d1) return fa_slab1d_local_plan(p->d1, g, which);
     return which ? p->cols[g] : p->rows[g];
+}
+
+struct fftw_amd_slab_plan_s *fa_slab_wrap1d(struct fa_slab1d *d, int ndev) {
+    struct fftw_amd_slab_plan_s *p = (struct fftw_amd_slab_plan_s *)calloc(1, sizeof(*p));
+    if (!p) return NULL;
+    p->ndev = ndev;
+    p->d1 = d;
+    return p;
 }

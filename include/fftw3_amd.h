@@ -134,6 +134,51 @@ int  fftw_amd_slab_num_devices(const fftw_amd_slab_plan p);
 fftw_plan fftw_amd_slab_local_plan(const fftw_amd_slab_plan p, int g, int which);   /* 0: rows plan, 1: column-block plan */
 void fftw_amd_destroy_slab_plan(fftw_amd_slab_plan p);
 
+/* ---- one long 1-D transform spread over the GPUs of a node (fftw3_amd/csrc/slab1d.c) -----------------------------
+   The reference's distributed 1-D solver (fftw/mpi/dft-rank1.c; fftw_mpi_local_size_1d / fftw_mpi_plan_dft_1d of
+   fftw/mpi/fftw3-mpi.h:97-138), devices of this process in the place of MPI ranks.  The result is an ordinary
+   fftw_amd_slab_plan: fftw_amd_slab_execute / _sync / _num_devices and fftw_amd_destroy_slab_plan work on it;
+   fftw_amd_slab_local_plan(p, g, 1) is device g's plan of the length-n0 columns, (p, g, 0) the one of the length-n1
+   rows.  Local plans get `flags` without the two SCRAMBLED bits and are guru64 plans (local arrays > 2^31 work).
+
+   Split.  n = n0 n1 with P | n0 and P | n1 (P = ndev); without such a split the planner returns NULL and
+   local_size_1d -1 (with P = 1 every n has one).  Rule, deterministic in (n, P, sign): among the admissible splits
+   whose ratio max(n0, n1) / min(n0, n1) is at most 4 times the smallest admissible ratio, take the one with the most
+   lengths that have register kernels (the two- and three-stage register-resident kernels of the library), then the
+   smallest ratio, then the larger n0.  BACKWARD uses the FORWARD split swapped
+   (fftw_amd_slab_split_1d reports it), which is what makes the two scrambled layouts below fit together.
+
+   Pipeline (w = n1 / P, h = n0 / P): exchange of column blocks of the input read as [n0][n1], w transforms of
+   length n0 down every block, a twiddle w_n^(k0 j1) by global position (kernels_slab.hip), exchange of row blocks,
+   h transforms of length n1 along the rows, and an exchange back into natural order.  Owned memory per device: two
+   buffers of n / P elements (one with SCRAMBLED_OUT) and a twiddle table of about 2 sqrt(n) elements.
+
+   Layouts (X = the transform of x):
+   - normal: device g holds the elements [g n / P, (g + 1) n / P) of x in in[g] and of X in out[g], so
+     local_ni = local_no = n / P.
+   - SCRAMBLED_OUT: device g holds [k0 in block g of n0][k1 in 0 .. n1), row-major; element (k0, k1) is X[k0 + n0 k1].
+   - SCRAMBLED_IN: in the plan's own split, device g holds [j1 in block g of n1][j0 in 0 .. n0), row-major; element
+     (j1, j0) is x[n1 j0 + j1].  For a BACKWARD plan this is exactly what the FORWARD SCRAMBLED_OUT plan of the same
+     n and P leaves, so FORWARD with SCRAMBLED_OUT followed by BACKWARD with SCRAMBLED_IN gives n x in normal order.
+   local_size_1d reports the block [g n / P, (g + 1) n / P) of whichever order applies.
+
+   NULL instead of a failure inside execute: ndev outside 1 ... 32, a named device that does not exist, a pair of
+   distinct devices without peer access, a row pitch (n0 or n1 elements) over hipDeviceAttributeMaxPitch, or a local
+   plan / buffer that cannot be made.  Planning works without a device (placeholder buffers: the plans can be
+   inspected, not executed). */
+#define FFTW_AMD_SLAB_SCRAMBLED_IN  (1U << 27)   /* same bits as FFTW_MPI_SCRAMBLED_IN / _OUT */
+#define FFTW_AMD_SLAB_SCRAMBLED_OUT (1U << 28)
+/* fftw_mpi_local_size_1d: elements device g's in / out arrays must hold; -1 when the plan would be NULL */
+long long fftw_amd_slab_local_size_1d(long long n, int ndev, int g, int sign, unsigned flags,
+                                      long long *local_ni, long long *local_i_start,
+                                      long long *local_no, long long *local_o_start);
+/* the split (n0, n1) the planner takes for (n, ndev, sign); 0 on success, -1 when there is none */
+int fftw_amd_slab_split_1d(long long n, int ndev, int sign, long long *n0, long long *n1);
+/* fftw_mpi_plan_dft_1d: in[g] / out[g] device arrays on devs[g] (devs == NULL: 0..ndev-1); in[g] == out[g] allowed */
+fftw_amd_slab_plan fftw_amd_slab_plan_dft_1d(long long n, int ndev, const int *devs,
+                                             fftw_complex *const *in, fftw_complex *const *out,
+                                             int sign, unsigned flags);
+
 /* ---- plan introspection used by the host-logic tests ------------------- */
 
 #define FFTW_AMD_MAX_DIMS 8
