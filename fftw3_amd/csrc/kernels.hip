@@ -18,6 +18,7 @@
 #include "common.hpp"
 
 #include "pass1024.hpp"
+#include "launch.hpp"
 
 /* ------------------------------------------------------------------------ */
 /* generic LDS pass kernel (runtime radices)                                 */
@@ -1162,94 +1163,47 @@ static void grid_for(i64 total, dim3 *grid) {
 }
 
 
-static std::atomic<unsigned> g_lds_attr_done{0};
-
 template <bool VIN, bool VOUT>
 static void launch_pass_variant(const PassArgs &pa, dim3 grid, size_t lds, hipStream_t st) {
     static int nth = 0;
     if (!nth) { const char *e = getenv("FFTW_AMD_GENERIC_THREADS"); nth = e ? atoi(e) : 256; if (nth < 64 || nth > 256) nth = 256; }
-    hipLaunchKernelGGL((pass_generic_kernel<VIN, VOUT>), grid, dim3(nth), lds, st, pa);
+    fa_launch_lds<pass_generic_kernel<VIN, VOUT>>(grid, dim3(nth), lds, 160 * 1024, st, pa);
 }
-
-/* kernels_rr.hip */
-int fa_launch_pass3tw(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                      i64 cs, i64 cn, hipStream_t st);          /* kernels_r3tw.hip */
-int fa_launch_pass3gw(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                      i64 cs, i64 cn, hipStream_t st);          /* kernels_r3w.hip */
-int fa_launch_pass3g(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                     i64 cs, i64 cn, hipStream_t st);
-int fa_launch_pass3t(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                     i64 cs, i64 cn, hipStream_t st);
-int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                      i64 cs, i64 cn, hipStream_t st);
-int fa_launch_pass3s(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                     i64 cs, i64 cn, hipStream_t st);
-int fa_launch_passrr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                     i64 cs, i64 cn, hipStream_t st);
-/* kernels_blue.hip */
-int fa_launch_blue(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                   i64 cs, i64 cn, hipStream_t st);
-/* kernels_r1.hip */
-int fa_launch_pass1r(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                     i64 cs, i64 cn, hipStream_t st);
 
 template <bool IN_T, bool OUT_T, int HAS_TW>
 static void launch_p1024_variant(const P1024Args &pa, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
     const size_t lds = FA_P1024_LDS_DOUBLES * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass1024_kernel<IN_T, OUT_T, HAS_TW>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL((pass1024_kernel<IN_T, OUT_T, HAS_TW>), grid, dim3(256), lds, st, pa);
+    fa_launch_lds<pass1024_kernel<IN_T, OUT_T, HAS_TW>>(grid, dim3(256), lds, lds, st, pa);
 }
 
 /* arguments of the register-resident 1024-point pass for one step and chunk; returns 1 if the step
    does not qualify (caller falls through to the generic kernel), 0 and *nblocks_out == 0 for an empty launch */
 static int fill_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
                       i64 cs, i64 cn, P1024Args &pa, i64 *nblocks_out, bool *in_t, bool *out_t, int *tw) {
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
     if (d->L != 1024 || d->src_im != 1 || d->dst_im != 1 ||
         (d->flags & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT | FFTW_AMD_F_CONJ_OUT)))
         return 1;
-    for (int i = 0; i < FFTW_AMD_MAX_DIMS; ++i) {
-        pa.dn[i] = (i < d->ndims) ? d->dim_n[i] : 1;
-        pa.dis[i] = (i < d->ndims) ? d->dim_is[i] : 0;
-        pa.dos[i] = (i < d->ndims) ? d->dim_os[i] : 0;
-        pa.dtw[i] = (i < d->ndims) ? d->dim_tw[i] : 0;
-    }
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        pa.dn[bd] = cn;
-    }
-    pa.src = bufs[d->src_buf] + sbase;
-    pa.dst = bufs[d->dst_buf] + dbase;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    if (!g.aligned() || !g.even_l() || !g.even_dims()) return 1;
+    fa_copy_dims(pa, g);
     pa.is_l = d->is_l;
     pa.os_l = d->os_l;
-    if (((uintptr_t)pa.src % 16) || ((uintptr_t)pa.dst % 16) || (pa.is_l % 2) || (pa.os_l % 2)) return 1;
-    for (int i = 0; i < d->ndims; ++i)
-        if ((pa.dis[i] % 2) || (pa.dos[i] % 2)) return 1;
     pa.w1024 = (const cplx *)tables[d->table];
     pa.tw_shift = d->tw_shift;
     pa.tw_lo = d->tw_n ? (const cplx *)tables[d->tw_lo] : NULL;
     pa.tw_hi = d->tw_n ? (const cplx *)tables[d->tw_hi] : NULL;
-    pa.ndims = d->ndims;
     pa.flags = d->flags;
     pa.lo_sh = 0; pa.lo_is = d->tile_lo_is; pa.lo_os = d->tile_lo_os;
     pa.dbg = NULL;
     if (d->tile_lo_n > 1) {
         if (d->tile_lo_n != 2 && d->tile_lo_n != 4) return 1;
         pa.lo_sh = d->tile_lo_n == 2 ? 1 : 2;
-        if ((pa.lo_is % 2) || (pa.lo_os % 2)) return 1;
+        if (!g.even_lo()) return 1;
     }
     pa.ntiles = (pa.dn[0] + (8 >> pa.lo_sh) - 1) / (8 >> pa.lo_sh);
-    i64 nblocks = pa.ntiles;
-    for (int i = 1; i < d->ndims; ++i) nblocks *= pa.dn[i];
-    if (nblocks > 0x7fffffffLL) return 1;
-    *nblocks_out = nblocks < 0 ? 0 : nblocks;
+    const StepBlocks nb = fa_step_blocks(pa);
+    if (nb.too_large()) return 1;
+    *nblocks_out = nb.empty() ? 0 : nb.n;
     *in_t = pa.dn[0] > 1 && iabs64(pa.dis[0]) <= iabs64(pa.is_l);
     *out_t = pa.dn[0] > 1 && iabs64(pa.dos[0]) <= iabs64(pa.os_l);
     *tw = d->tw_n == 0 ? 0 : ((d->flags & FFTW_AMD_F_TW_IN) ? 2 : 1);
@@ -1264,7 +1218,7 @@ static int launch_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *
     int tw;
     if (fill_p1024(d, bufs, tables, cs, cn, pa, &nblocks, &in_t, &out_t, &tw)) return 1;
     if (nblocks <= 0) return 0;
-    dim3 grid((unsigned)nblocks, 1, 1);
+    const dim3 grid((unsigned)nblocks, 1, 1);
 #define FA_P1024_CASE(I, O, W) if (in_t == I && out_t == O && tw == W) { launch_p1024_variant<I, O, W>(pa, grid, st); return 0; }
     FA_P1024_CASE(true, true, 0)  FA_P1024_CASE(true, true, 1)  FA_P1024_CASE(true, true, 2)
     FA_P1024_CASE(false, true, 0) FA_P1024_CASE(false, true, 1) FA_P1024_CASE(false, true, 2)
@@ -1335,14 +1289,9 @@ extern "C" int fa_hip_launch_pair1024(const fftw_amd_step_desc *d_second, double
     if ((cn2 > 0 && (i2 || !o2 || w2 != 2 || a2.lo_sh)) || (cn1 > 0 && (!i1 || !o1 || w1 != 0 || a1.lo_sh))) return 1;
     if (n1 + n2 <= 0) return 0;
     if (n1 + n2 > 0x7fffffffLL) return 1;
-    static std::atomic<unsigned> attr_done{0};
     const size_t lds = FA_P1024_LDS_DOUBLES * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass1024_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL(pass1024_pair_kernel, dim3((unsigned)(n1 + n2)), dim3(256), lds, (hipStream_t)stream,
-                       a2, a1, (unsigned)n2, (unsigned)n1);
+    fa_launch_lds<pass1024_pair_kernel>(dim3((unsigned)(n1 + n2)), dim3(256), lds, lds, (hipStream_t)stream,
+                                        a2, a1, (unsigned)n2, (unsigned)n1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { fprintf(stderr, "fftw3_amd: pair launch failed: %s\n", hipGetErrorString(e)); return -1; }
     return 0;
@@ -1367,21 +1316,8 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
     if (d->variant == FFTW_AMD_K_R3 && (fa_launch_pass3s(d, bufs, tables, cs, cn, st) == 0 ||
                                         fa_launch_pass3g(d, bufs, tables, cs, cn, st) == 0 ||
                                         fa_launch_pass3t(d, bufs, tables, cs, cn, st) == 0)) return 0;
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
-    for (int i = 0; i < FFTW_AMD_MAX_DIMS; ++i) {
-        pa.dn[i] = (i < d->ndims) ? d->dim_n[i] : 1;
-        pa.dis[i] = (i < d->ndims) ? d->dim_is[i] : 0;
-        pa.dos[i] = (i < d->ndims) ? d->dim_os[i] : 0;
-        pa.dtw[i] = (i < d->ndims) ? d->dim_tw[i] : 0;
-    }
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        pa.dn[bd] = cn;
-    }
-    pa.src = bufs[d->src_buf] + sbase;
-    pa.dst = bufs[d->dst_buf] + dbase;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    fa_copy_dims(pa, g);
     pa.src_im = d->src_im;
     pa.dst_im = d->dst_im;
     pa.is_l = d->is_l;
@@ -1394,7 +1330,6 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
     pa.L = d->L;
     pa.nrad = d->nradices;
     for (int i = 0; i < FFTW_AMD_MAX_RADICES; ++i) pa.rad[i] = (i < d->nradices) ? d->radices[i] : 1;
-    pa.ndims = d->ndims;
     pa.T = d->tile;
     pa.lo_n = d->tile_lo_n > 1 ? d->tile_lo_n : 1;
     pa.lo_is = d->tile_lo_is; pa.lo_os = d->tile_lo_os;
@@ -1408,44 +1343,23 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
     pa.in_t_fast = (pa.dn[0] > 1 && iabs64(pa.dis[0]) <= iabs64(pa.is_l)) || pa.L == 1;
     pa.out_t_fast = (pa.dn[0] > 1 && iabs64(pa.dos[0]) <= iabs64(pa.os_l)) || pa.L == 1;
 
-    i64 nblocks = pa.ntiles;
-    for (int i = 1; i < d->ndims; ++i) nblocks *= pa.dn[i];
-    if (nblocks <= 0) return 0;
-    dim3 grid;
-    if (nblocks <= 0x7fffffffLL) grid = dim3((unsigned)nblocks, 1, 1);
-    else {
+    const StepBlocks nb = fa_step_blocks(pa);
+    if (nb.empty()) return 0;
+    dim3 grid = nb.grid();
+    if (nb.too_large()) {
         /* split over y; the kernel recombines.  nblocks must factor: use 65535-ish rows */
-        unsigned gy = (unsigned)((nblocks + 0x3fffffffLL) / 0x40000000LL);
-        while (nblocks % gy) ++gy;
-        grid = dim3((unsigned)(nblocks / gy), gy, 1);
+        unsigned gy = (unsigned)((nb.n + 0x3fffffffLL) / 0x40000000LL);
+        while (nb.n % gy) ++gy;
+        grid = dim3((unsigned)(nb.n / gy), gy, 1);
     }
     size_t lds = (size_t)2 * pa.L * pa.ld * sizeof(cplx);
     if (lds > 160 * 1024) {
         fprintf(stderr, "fftw3_amd: internal error: pass tile needs %zu B of LDS\n", lds);
         return -1;
     }
-    if (fa_attr_needed(g_lds_attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass_generic_kernel<false, false>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FA_CHECK(hipFuncSetAttribute((const void *)pass_generic_kernel<true, false>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FA_CHECK(hipFuncSetAttribute((const void *)pass_generic_kernel<false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FA_CHECK(hipFuncSetAttribute((const void *)pass_generic_kernel<true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        fa_attr_set(g_lds_attr_done);
-    }
     /* 16-byte vector access when the element is an aligned interleaved pair */
-    bool vin = d->src_im == 1 && !(d->flags & FFTW_AMD_F_REAL_IN) &&
-               ((uintptr_t)pa.src % 16 == 0) && (pa.is_l % 2 == 0);
-    bool vout = d->dst_im == 1 && !(d->flags & FFTW_AMD_F_REAL_OUT) &&
-                ((uintptr_t)pa.dst % 16 == 0) && (pa.os_l % 2 == 0);
-    for (int i = 0; i < d->ndims; ++i) {
-        if (pa.dis[i] % 2) vin = false;
-        if (pa.dos[i] % 2) vout = false;
-    }
-    if (pa.lo_is % 2) vin = false;
-    if (pa.lo_os % 2) vout = false;
+    const bool vin = d->src_im == 1 && !(d->flags & FFTW_AMD_F_REAL_IN) && g.src16 && g.is_l_even && g.dis_even && g.lo_is_even;
+    const bool vout = d->dst_im == 1 && !(d->flags & FFTW_AMD_F_REAL_OUT) && g.dst16 && g.os_l_even && g.dos_even && g.lo_os_even;
     {
         /* all radices have register butterflies and the tile is at most 4096
            elements: the single-image kernel (two workgroups per CU) */
@@ -1457,19 +1371,11 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
                 d->radices[i] == 12 || d->radices[i] == 14 || d->radices[i] == 15) small_radices = false;
         /* ping-pong images that fit twice on a CU need no help; larger tiles take the single image */
         if (inplace_mode && small_radices && (i64)pa.L * pa.T <= 4096 && lds > 80 * 1024) {
-            static std::atomic<unsigned> done{0};
-            size_t lds1 = (size_t)pa.L * pa.ld * sizeof(cplx);
-            if (fa_attr_needed(done)) {
-                FA_CHECK(hipFuncSetAttribute((const void *)pass_inplace_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                FA_CHECK(hipFuncSetAttribute((const void *)pass_inplace_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                FA_CHECK(hipFuncSetAttribute((const void *)pass_inplace_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                FA_CHECK(hipFuncSetAttribute((const void *)pass_inplace_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                fa_attr_set(done);
-            }
-            if (vin && vout) hipLaunchKernelGGL((pass_inplace_kernel<true, true>), grid, dim3(256), lds1, st, pa);
-            else if (vin) hipLaunchKernelGGL((pass_inplace_kernel<true, false>), grid, dim3(256), lds1, st, pa);
-            else if (vout) hipLaunchKernelGGL((pass_inplace_kernel<false, true>), grid, dim3(256), lds1, st, pa);
-            else hipLaunchKernelGGL((pass_inplace_kernel<false, false>), grid, dim3(256), lds1, st, pa);
+            const size_t lds1 = (size_t)pa.L * pa.ld * sizeof(cplx);
+            if (vin && vout) fa_launch_lds<pass_inplace_kernel<true, true>>(grid, dim3(256), lds1, 160 * 1024, st, pa);
+            else if (vin) fa_launch_lds<pass_inplace_kernel<true, false>>(grid, dim3(256), lds1, 160 * 1024, st, pa);
+            else if (vout) fa_launch_lds<pass_inplace_kernel<false, true>>(grid, dim3(256), lds1, 160 * 1024, st, pa);
+            else fa_launch_lds<pass_inplace_kernel<false, false>>(grid, dim3(256), lds1, 160 * 1024, st, pa);
             return 0;
         }
     }
@@ -1524,14 +1430,9 @@ static int elem_fill(ElemIdx *e, const fftw_amd_step_desc *d, i64 K, i64 cn, int
 
 static int fill_copy_args(CopyArgs *ca, const fftw_amd_step_desc *d, double *const *bufs,
                           void *const *tables, i64 cs, i64 cn, dim3 *grid) {
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-    }
-    ca->src = bufs[d->src_buf] + sbase;
-    ca->dst = bufs[d->dst_buf] + dbase;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    ca->src = g.src;
+    ca->dst = g.dst;
     ca->src_im = d->src_im;
     ca->dst_im = d->dst_im;
     ca->is_k = d->is_l;
@@ -1597,14 +1498,10 @@ static int launch_step_kind(const fftw_amd_step_desc *d, double *const *bufs,
     case FFTW_AMD_STEP_R2C_POST:
     case FFTW_AMD_STEP_C2R_PRE: {
         RealArgs ra;
-        int bd = d->batch_dim;
-        i64 sbase = d->src_base, dbase = d->dst_base;
-        if (bd >= 0) {
-            sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-            dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        }
-        ra.src = bufs[d->src_buf] + sbase;
-        ra.dst = bufs[d->dst_buf] + dbase;
+        const int bd = d->batch_dim;
+        const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+        ra.src = g.src;
+        ra.dst = g.dst;
         ra.src_im = d->src_im;
         ra.dst_im = d->dst_im;
         ra.is_k = d->is_l;
@@ -1683,14 +1580,10 @@ static int launch_step_kind(const fftw_amd_step_desc *d, double *const *bufs,
     case FFTW_AMD_STEP_R2C_POST4:
     case FFTW_AMD_STEP_C2R_PRE4: {
         Real4Args ra;
-        int bd = d->batch_dim;
-        i64 sbase = d->src_base, dbase = d->dst_base;
-        if (bd >= 0) {
-            sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-            dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        }
-        ra.src = bufs[d->src_buf] + sbase;
-        ra.dst = bufs[d->dst_buf] + dbase;
+        const int bd = d->batch_dim;
+        const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+        ra.src = g.src;
+        ra.dst = g.dst;
         ra.src_im = d->src_im;
         ra.dst_im = d->dst_im;
         ra.is_k = d->is_l;
@@ -1741,14 +1634,10 @@ static int launch_step_kind(const fftw_amd_step_desc *d, double *const *bufs,
     }
     case FFTW_AMD_STEP_R2R: {
         R2RArgs ra;
-        int bd = d->batch_dim;
-        i64 sbase = d->src_base, dbase = d->dst_base;
-        if (bd >= 0) {
-            sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-            dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        }
-        ra.src = bufs[d->src_buf] + sbase;
-        ra.dst = bufs[d->dst_buf] + dbase;
+        const int bd = d->batch_dim;
+        const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+        ra.src = g.src;
+        ra.dst = g.dst;
         ra.src_im = d->src_im;
         ra.dst_im = d->dst_im;
         ra.is_k = d->is_l;

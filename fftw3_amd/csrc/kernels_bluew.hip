@@ -10,19 +10,14 @@
 #include "pass3s.hpp"
 #include "pass3g.hpp"
 #include "pass3b.hpp"
+#include "launch.hpp"
 
 template <int R1, int R2, int R3>
 static void launch_bluew(const BlueArgs &ba, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
     typedef P3GGeom<R1, R2, R3, 512> G;
     static_assert(G::fits && G::T == 1, "menu entry exceeds the per-item element budget");
     const size_t lds = G::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)blue3g_kernel<R1, R2, R3, 512>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL((blue3g_kernel<R1, R2, R3, 512>), grid, dim3(512), lds, st, ba);
+    fa_launch_lds<blue3g_kernel<R1, R2, R3, 512>>(grid, dim3(512), lds, lds, st, ba);
 }
 
 /* smallest padded length >= need among the wide kernels (0: none) */

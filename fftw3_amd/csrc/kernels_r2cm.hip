@@ -8,20 +8,13 @@
 #include "pass1024.hpp"
 #include "passrr.hpp"
 #include "r2crows.hpp"
+#include "launch.hpp"
 
 template <int R1, int R2>
 static void launch_r2cr_m(const R2CRArgs &ra, dim3 grid, hipStream_t st, bool inverse) {
-    static std::atomic<unsigned> attr_done{0};
     const size_t lds = R2CRGeom<R1, R2>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)r2crows_kernel<R1, R2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        FA_CHECK(hipFuncSetAttribute((const void *)c2rrows_kernel<R1, R2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    if (inverse) hipLaunchKernelGGL((c2rrows_kernel<R1, R2>), grid, dim3(256), lds, st, ra);
-    else hipLaunchKernelGGL((r2crows_kernel<R1, R2>), grid, dim3(256), lds, st, ra);
+    if (inverse) fa_launch_lds<c2rrows_kernel<R1, R2>>(grid, dim3(256), lds, lds, st, ra);
+    else fa_launch_lds<r2crows_kernel<R1, R2>>(grid, dim3(256), lds, lds, st, ra);
 }
 
 /* rows per tile for half length L (0: none) */

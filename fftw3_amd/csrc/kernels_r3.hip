@@ -10,21 +10,14 @@
 #include "pass3s.hpp"
 #include "pass3g.hpp"
 #include "r2crows.hpp"
+#include "launch.hpp"
 
 template <int R1, int R2, int R3>
 static void launch_3g(const P3SArgs &pa, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
     static_assert(P3GGeom<R1, R2, R3>::fits, "menu entry exceeds the per-item element budget");
     const size_t lds = P3GGeom<R1, R2, R3>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass3g_kernel<R1, R2, R3>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL((pass3g_kernel<R1, R2, R3>), grid, dim3(256), lds, st, pa);
+    fa_launch_lds<pass3g_kernel<R1, R2, R3>>(grid, dim3(256), lds, lds, st, pa);
 }
-
-extern "C" int fa_hip_r3w_has(int L);              /* kernels_r3w.hip */
 
 /* rows per tile of the three-stage kernel for length L (0: none).  2048 / 4096 / 8192 are the
    tuned pass3s kernels of kernels_rr.hip. */
@@ -44,39 +37,22 @@ extern "C" int fa_hip_r3_tile(int L) {
 int fa_launch_pass3g(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
                      i64 cs, i64 cn, hipStream_t st) {
     P3SArgs pa;
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
     const int T = fa_hip_r3_tile(d->L);
     if (T <= 0 || d->L == 2048 || d->L == 4096 || d->L == 8192 || d->L == 16384 || (d->L > 8192 && fa_hip_r3w_has(d->L)) || d->tile != T || d->src_im != 1 || d->dst_im != 1 ||
         d->tw_n || d->is_l != 2 || d->os_l != 2 || d->tile_lo_n > 1 ||
         (d->flags & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT | FFTW_AMD_F_CONJ_OUT)))
         return 1;
-    for (int i = 0; i < FFTW_AMD_MAX_DIMS; ++i) {
-        pa.dn[i] = (i < d->ndims) ? d->dim_n[i] : 1;
-        pa.dis[i] = (i < d->ndims) ? d->dim_is[i] : 0;
-        pa.dos[i] = (i < d->ndims) ? d->dim_os[i] : 0;
-    }
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        pa.dn[bd] = cn;
-    }
-    pa.src = bufs[d->src_buf] + sbase;
-    pa.dst = bufs[d->dst_buf] + dbase;
-    if (((uintptr_t)pa.src % 16) || ((uintptr_t)pa.dst % 16)) return 1;
-    for (int i = 0; i < d->ndims; ++i)
-        if ((pa.dis[i] % 2) || (pa.dos[i] % 2)) return 1;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    if (!g.aligned() || !g.even_dims()) return 1;
+    fa_copy_dims(pa, g);
     pa.wL = (const cplx *)tables[d->table];
-    pa.ndims = d->ndims;
     pa.flags = d->flags;
     pa.ntiles = (pa.dn[0] + T - 1) / T;
-    i64 nblocks = pa.ntiles;
-    for (int i = 1; i < d->ndims; ++i) nblocks *= pa.dn[i];
-    if (nblocks <= 0) return 0;
-    if (nblocks > 0x7fffffffLL) return 1;
-    dim3 grid((unsigned)nblocks, 1, 1);
+    const StepBlocks nb = fa_step_blocks(pa);
+    if (nb.empty()) return 0;
+    if (nb.too_large()) return 1;
     switch (d->L) {
-#define X(L_, R1_, R2_, R3_) case L_: launch_3g<R1_, R2_, R3_>(pa, grid, st); return 0;
+#define X(L_, R1_, R2_, R3_) case L_: launch_3g<R1_, R2_, R3_>(pa, nb.grid(), st); return 0;
 #include "r3_menu.inc"
 #undef X
     }
@@ -87,15 +63,9 @@ int fa_launch_pass3g(const fftw_amd_step_desc *d, double *const *bufs, void *con
 
 template <int R1, int R2, int R3, bool IN_T, int TW>
 static void launch_3t_variant(const P1024Args &pa, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
     static_assert(P3TGeom<R1, R2, R3>::fits, "menu entry exceeds the per-item element budget");
     const size_t lds = P3TGeom<R1, R2, R3>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass3t_kernel<R1, R2, R3, IN_T, TW>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL((pass3t_kernel<R1, R2, R3, IN_T, TW>), grid, dim3(256), lds, st, pa);
+    fa_launch_lds<pass3t_kernel<R1, R2, R3, IN_T, TW>>(grid, dim3(256), lds, lds, st, pa);
 }
 
 /* column passes (T,T) without / with output twiddle, transposed last passes (L,T) without /
@@ -114,8 +84,6 @@ static int dispatch_3t(const P1024Args &pa, dim3 grid, hipStream_t st, bool in_t
     return 1;
 }
 
-extern "C" int fa_hip_r3tw_tile(int L);            /* kernels_r3tw.hip: the 512-item forms */
-
 /* sequences per tile of the strided three-stage kernel for length L (0: none); lengths with a 512-item form
    (kernels_r3tw.hip) report that form's tile -- it is the one the executor launches */
 extern "C" int fa_hip_r3t_tile(int L) {
@@ -131,45 +99,28 @@ extern "C" int fa_hip_r3t_tile(int L) {
 int fa_launch_pass3t(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
                      i64 cs, i64 cn, hipStream_t st) {
     P1024Args pa;
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
     const int T = fa_hip_r3t_tile(d->L);
     if (d->L > 1024 && fa_hip_r3tw_tile(d->L) > 0) return 1;      /* the 512-item form: fa_launch_pass3tw */
     if (T <= 0 || d->tile != T || d->src_im != 1 || d->dst_im != 1 || d->tile_lo_n > 1 ||
         (d->flags & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT | FFTW_AMD_F_CONJ_OUT)))
         return 1;
-    for (int i = 0; i < FFTW_AMD_MAX_DIMS; ++i) {
-        pa.dn[i] = (i < d->ndims) ? d->dim_n[i] : 1;
-        pa.dis[i] = (i < d->ndims) ? d->dim_is[i] : 0;
-        pa.dos[i] = (i < d->ndims) ? d->dim_os[i] : 0;
-        pa.dtw[i] = (i < d->ndims) ? d->dim_tw[i] : 0;
-    }
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        pa.dn[bd] = cn;
-    }
-    pa.src = bufs[d->src_buf] + sbase;
-    pa.dst = bufs[d->dst_buf] + dbase;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    if (!g.aligned() || !g.even_l() || !g.even_dims()) return 1;
+    fa_copy_dims(pa, g);
     pa.is_l = d->is_l;
     pa.os_l = d->os_l;
-    if (((uintptr_t)pa.src % 16) || ((uintptr_t)pa.dst % 16) || (pa.is_l % 2) || (pa.os_l % 2)) return 1;
-    for (int i = 0; i < d->ndims; ++i)
-        if ((pa.dis[i] % 2) || (pa.dos[i] % 2)) return 1;
     pa.w1024 = (const cplx *)tables[d->table];
     pa.tw_shift = d->tw_shift;
     pa.tw_lo = d->tw_n ? (const cplx *)tables[d->tw_lo] : NULL;
     pa.tw_hi = d->tw_n ? (const cplx *)tables[d->tw_hi] : NULL;
-    pa.ndims = d->ndims;
     pa.flags = d->flags;
     pa.lo_sh = 0; pa.lo_is = 0; pa.lo_os = 0;
     pa.ntiles = (pa.dn[0] + T - 1) / T;
-    i64 nblocks = pa.ntiles;
-    for (int i = 1; i < d->ndims; ++i) nblocks *= pa.dn[i];
-    if (nblocks <= 0) return 0;
-    if (nblocks > 0x7fffffffLL) return 1;
+    const StepBlocks nb = fa_step_blocks(pa);
+    if (nb.empty()) return 0;
+    if (nb.too_large()) return 1;
     if (pa.dn[0] * 4 < T) return 1;              /* a mostly empty tile: the LDS kernel */
-    dim3 grid((unsigned)nblocks, 1, 1);
+    const dim3 grid = nb.grid();
     bool in_t = pa.dn[0] > 1 && iabs64(pa.dis[0]) <= iabs64(pa.is_l);
     bool out_t = pa.dn[0] > 1 && iabs64(pa.dos[0]) <= iabs64(pa.os_l);
     int tw = d->tw_n == 0 ? 0 : ((d->flags & FFTW_AMD_F_TW_IN) ? 2 : 1);
@@ -185,17 +136,9 @@ int fa_launch_pass3t(const fftw_amd_step_desc *d, double *const *bufs, void *con
 
 template <int R1, int R2>
 static void launch_r2cr(const R2CRArgs &ra, dim3 grid, hipStream_t st, bool inverse) {
-    static std::atomic<unsigned> attr_done{0};
     const size_t lds = R2CRGeom<R1, R2>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)r2crows_kernel<R1, R2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        FA_CHECK(hipFuncSetAttribute((const void *)c2rrows_kernel<R1, R2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    if (inverse) hipLaunchKernelGGL((c2rrows_kernel<R1, R2>), grid, dim3(256), lds, st, ra);
-    else hipLaunchKernelGGL((r2crows_kernel<R1, R2>), grid, dim3(256), lds, st, ra);
+    if (inverse) fa_launch_lds<c2rrows_kernel<R1, R2>>(grid, dim3(256), lds, lds, st, ra);
+    else fa_launch_lds<r2crows_kernel<R1, R2>>(grid, dim3(256), lds, lds, st, ra);
 }
 
 extern "C" int fa_hip_r2c_rows_tile(int L) {
@@ -212,14 +155,6 @@ extern "C" int fa_hip_r2c_rows_tile(int L) {
 /* A step with FFTW_AMD_F_R2C_ROWS / FFTW_AMD_F_C2R_ROWS has no other executor: the planner only emits it for
    layouts this kernel takes (r2c_rows_layout_ok), so anything else here is a caller error
    (new-array execution with differently aligned arrays) and fails loudly. */
-int fa_launch_r2crows1(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                       i64 cs, i64 cn, hipStream_t st);
-extern "C" int fa_hip_r2c_rows2m_tile(int L);      /* kernels_r2cm.hip: mixed-radix two-stage lengths, plain r2c / c2r */
-int fa_launch_r2crows2m(int L, const R2CRArgs &ra, dim3 grid, hipStream_t st, bool inverse);
-extern "C" int fa_hip_r2c_rows3_tile(int L);
-int fa_launch_r2crows3(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
-                       i64 cs, i64 cn, hipStream_t st);
-
 int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
                       i64 cs, i64 cn, hipStream_t st) {
     /* half lengths above 1024: the three-stage form (kernels_rr.hip) */
@@ -228,8 +163,6 @@ int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *co
     if (fa_hip_r2c_rows_tile(d->L) <= 0 && !mixed2 && fa_hip_r2c_rows3_tile(d->L) > 0)
         return fa_launch_r2crows3(d, bufs, tables, cs, cn, st);
     R2CRArgs ra;
-    int bd = d->batch_dim;
-    i64 sbase = d->src_base, dbase = d->dst_base;
     const int T = mixed2 ? fa_hip_r2c_rows2m_tile(d->L) : fa_hip_r2c_rows_tile(d->L);
     const bool fwd = (d->flags & FFTW_AMD_F_R2C_ROWS) != 0;
     const int epi = (int)d->aux_valid;                 /* fused r2r epilogue (r2c) / prologue (c2r), or 0 */
@@ -241,18 +174,8 @@ int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *co
         fprintf(stderr, "fftw3_amd: internal error: fused r2c rows step with an unsupported layout\n");
         abort();
     }
-    for (int i = 0; i < FFTW_AMD_MAX_DIMS; ++i) {
-        ra.dn[i] = (i < d->ndims) ? d->dim_n[i] : 1;
-        ra.dis[i] = (i < d->ndims) ? d->dim_is[i] : 0;
-        ra.dos[i] = (i < d->ndims) ? d->dim_os[i] : 0;
-    }
-    if (bd >= 0) {
-        sbase += chunk_adv(d->src_buf, cs, d->dim_is[bd]);
-        dbase += chunk_adv(d->dst_buf, cs, d->dim_os[bd]);
-        ra.dn[bd] = cn;
-    }
-    ra.src = bufs[d->src_buf] + sbase;
-    ra.dst = bufs[d->dst_buf] + dbase;
+    const StepGeom g = fa_step_geom(d, bufs, cs, cn);
+    fa_copy_dims(ra, g);
     ra.os_k = d->os_l;
     ra.dst_im = d->dst_im;
     ra.is_k = d->is_l;
@@ -263,7 +186,7 @@ int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *co
     ra.post = post;
     ra.twmul = (epi && d->aux_base > 0) ? (int)d->aux_base : 1;
     ra.rn = epi == FFTW_AMD_R2R_POST_E00 ? d->aux_n / 2 + 1 : (epi == FFTW_AMD_R2R_POST_O00 ? d->aux_n / 2 - 1 : d->aux_n);
-    if ((!real_src && ((uintptr_t)ra.src % 16)) || (!real_dst && ((uintptr_t)ra.dst % 16))) {
+    if ((!real_src && !g.src16) || (!real_dst && !g.dst16)) {
         fprintf(stderr, "fftw3_amd: fftw_execute_dft_r2c needs arrays aligned like the ones the plan was "
                         "created with (16 bytes)\n");
         abort();
@@ -272,17 +195,14 @@ int fa_launch_r2crows(const fftw_amd_step_desc *d, double *const *bufs, void *co
     ra.tw_lo = (const cplx *)tables[d->tw_lo];
     ra.tw_hi = (const cplx *)tables[d->tw_hi];
     ra.tw_shift = d->tw_shift;
-    ra.ndims = d->ndims;
     ra.ntiles = (ra.dn[0] + T - 1) / T;
-    i64 nblocks = ra.ntiles;
-    for (int i = 1; i < d->ndims; ++i) nblocks *= ra.dn[i];
-    if (nblocks <= 0) return 0;
-    dim3 grid;
-    if (nblocks <= 0x7fffffffLL) grid = dim3((unsigned)nblocks, 1, 1);
-    else {
-        unsigned gy = (unsigned)((nblocks + 0x3fffffffLL) / 0x40000000LL);
-        while (nblocks % gy) ++gy;
-        grid = dim3((unsigned)(nblocks / gy), gy, 1);
+    const StepBlocks nb = fa_step_blocks(ra);
+    if (nb.empty()) return 0;
+    dim3 grid = nb.grid();
+    if (nb.too_large()) {
+        unsigned gy = (unsigned)((nb.n + 0x3fffffffLL) / 0x40000000LL);
+        while (nb.n % gy) ++gy;
+        grid = dim3((unsigned)(nb.n / gy), gy, 1);
     }
     const bool inverse = (d->flags & FFTW_AMD_F_C2R_ROWS) != 0;
     switch (d->L) {

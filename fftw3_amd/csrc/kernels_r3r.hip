@@ -8,25 +8,15 @@
 #include "passrr.hpp"
 #include "pass3s.hpp"
 #include "pass3g.hpp"
+#include "launch.hpp"
 
 template <int R1, int R2, int R3>
 static void launch_3g_real(const P3SArgs &pa, dim3 grid, hipStream_t st, bool inverse) {
-    static std::atomic<unsigned> attr_done{0};
     static_assert(P3GGeom<R1, R2, R3>::fits, "menu entry exceeds the per-item element budget");
     const size_t lds = P3GGeom<R1, R2, R3>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)pass3g_kernel<R1, R2, R3, 1>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        FA_CHECK(hipFuncSetAttribute((const void *)pass3g_kernel<R1, R2, R3, 2>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    if (inverse) hipLaunchKernelGGL((pass3g_kernel<R1, R2, R3, 2>), grid, dim3(256), lds, st, pa);
-    else hipLaunchKernelGGL((pass3g_kernel<R1, R2, R3, 1>), grid, dim3(256), lds, st, pa);
+    if (inverse) fa_launch_lds<pass3g_kernel<R1, R2, R3, 2>>(grid, dim3(256), lds, lds, st, pa);
+    else fa_launch_lds<pass3g_kernel<R1, R2, R3, 1>>(grid, dim3(256), lds, lds, st, pa);
 }
-
-extern "C" int fa_hip_r2c_rows3gw_has(int L);     /* kernels_r3w.hip: the 512-item forms for half lengths above 8192 */
-int fa_launch_r2crows3gw(int L, const P3SArgs &pa, dim3 grid, hipStream_t st, bool inverse);
 
 /* rows per tile of the fused real form for half length L (0: none) */
 extern "C" int fa_hip_r2c_rows3g_tile(int L) {

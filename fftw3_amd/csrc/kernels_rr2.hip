@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "pass1024.hpp"
 #include "passrr.hpp"
+#include "launch.hpp"
 #include "rr_dispatch.hpp"
 
 template <int L_, int R1_, int R2_>

@@ -13,14 +13,8 @@
 
 template <int R1, int R2, bool IN_T, bool OUT_T, int TW>
 static void launch_rr_variant(const P1024Args &pa, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
     const size_t lds = RRGeom<R1, R2>::lds_doubles * sizeof(double);
-    if (fa_attr_needed(attr_done)) {
-        FA_CHECK(hipFuncSetAttribute((const void *)passrr_kernel<R1, R2, IN_T, OUT_T, TW>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        fa_attr_set(attr_done);
-    }
-    hipLaunchKernelGGL((passrr_kernel<R1, R2, IN_T, OUT_T, TW>), grid, dim3(256), lds, st, pa);
+    fa_launch_lds<passrr_kernel<R1, R2, IN_T, OUT_T, TW>>(grid, dim3(256), lds, lds, st, pa);
 }
 
 /* the lane mappings that occur in plans: column passes (T,T) with any twiddle
