@@ -155,6 +155,14 @@ _sig("fftw_amd_slab_sync", None, _vp)
 _sig("fftw_amd_slab_num_devices", C.c_int, _vp)
 _sig("fftw_amd_slab_local_plan", _vp, _vp, C.c_int, C.c_int)
 _sig("fftw_amd_destroy_slab_plan", None, _vp)
+_sig("fftw_amd_slab_local_size_transposed", C.c_longlong, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.c_int,
+     C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
+_sig("fftw_amd_slab_plan_dft_r2c", _vp, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int), _vpp, _vpp, C.c_uint)
+_sig("fftw_amd_slab_plan_dft_c2r", _vp, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int), _vpp, _vpp, C.c_uint)
+_sig("fftw_amd_slab_exchange_ops", C.c_int, _vp, C.c_int, C.POINTER(C.c_longlong), C.c_int)
+_sig("fftw_amd_slab_block_transpose", C.c_int, _vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int,
+     C.POINTER(C.c_longlong), C.c_int, _vp)
+_sig("fftw_amd_slab_execute_timed", C.c_int, _vp, C.POINTER(C.c_double))
 _sig("fftw_amd_slab_local_size_1d", C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_uint,
      C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
 _sig("fftw_amd_slab_split_1d", C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
@@ -665,8 +673,23 @@ def slab_local_size(n, ndev, g):
     return tot, ln0.value, lo.value
 
 
+SLAB_TRANSPOSED_IN = 1 << 29
+SLAB_TRANSPOSED_OUT = 1 << 30
+SLAB_OP_FIELDS = ("sbuf", "sdev", "soff", "dbuf", "ddev", "doff", "A", "B", "I", "ssa", "ssb", "dsa", "dsb")
+
+
+def slab_local_size_transposed(n, ndev, g):
+    """fftw_amd_slab_local_size_transposed: (elements, local_n0, local_0_start, local_n1, local_1_start) of device g;
+    n holds the COMPLEX dimensions (n_last / 2 + 1 as the last one for real data)"""
+    nn = (C.c_longlong * len(n))(*n)
+    v = [C.c_longlong(0) for _ in range(4)]
+    tot = lib.fftw_amd_slab_local_size_transposed(len(n), nn, ndev, g, *[C.byref(x) for x in v])
+    return (tot,) + tuple(x.value for x in v)
+
+
 class SlabPlanC(object):
-    """fftw_amd_slab_plan_dft: a 2-D / 3-D complex transform whose first dimension is cut over several devices"""
+    """fftw_amd_slab_plan_dft: a 2-D / 3-D complex transform whose first dimension is cut over several devices;
+    flags may carry SLAB_TRANSPOSED_IN / SLAB_TRANSPOSED_OUT (layouts in include/fftw3_amd.h)"""
 
     def __init__(self, n, devs, ins, outs, sign, flags=ESTIMATE):
         nn = (C.c_longlong * len(n))(*n)
@@ -676,6 +699,17 @@ class SlabPlanC(object):
             raise ValueError("slab planner returned NULL (invalid or unsupported problem)")
         self._keep = (ins, outs)
 
+    def exchange_ops(self, which):
+        """fftw_amd_slab_exchange_ops: the block moves of exchange `which` as dicts keyed by SLAB_OP_FIELDS, in the
+        executor's order; None when the plan has no such exchange"""
+        n = lib.fftw_amd_slab_exchange_ops(self.handle, which, None, 0)
+        if n < 0:
+            return None
+        buf = (C.c_longlong * (max(n, 1) * len(SLAB_OP_FIELDS)))()
+        lib.fftw_amd_slab_exchange_ops(self.handle, which, buf, n)
+        k = len(SLAB_OP_FIELDS)
+        return [dict(zip(SLAB_OP_FIELDS, buf[i * k:(i + 1) * k])) for i in range(n)]
+
     def execute(self):
         if device_count() <= 0:
             raise RuntimeError("no HIP device: the slab plan cannot execute (no CPU fallback)")
@@ -683,6 +717,13 @@ class SlabPlanC(object):
 
     def sync(self):
         lib.fftw_amd_slab_sync(self.handle)
+
+    def execute_timed(self):
+        """fftw_amd_slab_execute_timed: one execution between device events, milliseconds"""
+        ms = C.c_double(0.0)
+        if device_count() <= 0 or lib.fftw_amd_slab_execute_timed(self.handle, C.byref(ms)):
+            raise RuntimeError("the slab plan cannot be timed (no HIP device, or a 1-D plan)")
+        return ms.value
 
     def local_plan_sprint(self, g, which):
         h = lib.fftw_amd_slab_local_plan(self.handle, g, which)
@@ -694,6 +735,18 @@ class SlabPlanC(object):
         finally:
             lib.fftw_free(s)
 
+    def local_plan_steps(self, g, which):
+        """the step descriptors of device g's local plan (which = 0: trailing dimensions, 1: length n0); None: no plan"""
+        h = lib.fftw_amd_slab_local_plan(self.handle, g, which)
+        if not h:
+            return None
+        out = []
+        for i in range(lib.fftw_amd_plan_num_steps(h)):
+            d = StepDesc()
+            lib.fftw_amd_plan_get_step(h, i, C.byref(d))
+            out.append(d)
+        return out
+
     def destroy(self):
         if self.handle:
             lib.fftw_amd_destroy_slab_plan(self.handle)
@@ -704,6 +757,43 @@ class SlabPlanC(object):
             self.destroy()
         except Exception:
             pass
+
+
+class SlabPlanR2cC(SlabPlanC):
+    """fftw_amd_slab_plan_dft_r2c: n is the logical real size; ins[g] real rows padded to 2 (n_last / 2 + 1), outs[g]
+    complex; flags may carry SLAB_TRANSPOSED_OUT"""
+
+    def __init__(self, n, devs, ins, outs, flags=ESTIMATE):
+        nn = (C.c_longlong * len(n))(*n)
+        dv = (C.c_int * len(devs))(*devs)
+        self.handle = lib.fftw_amd_slab_plan_dft_r2c(len(n), nn, len(devs), dv, _ptrs(ins), _ptrs(outs), flags)
+        if not self.handle:
+            raise ValueError("r2c slab planner returned NULL (invalid or unsupported problem)")
+        self._keep = (ins, outs)
+
+
+class SlabPlanC2rC(SlabPlanC):
+    """fftw_amd_slab_plan_dft_c2r: the reverse, unnormalised; flags may carry SLAB_TRANSPOSED_IN; the complex input may
+    be overwritten"""
+
+    def __init__(self, n, devs, ins, outs, flags=ESTIMATE):
+        nn = (C.c_longlong * len(n))(*n)
+        dv = (C.c_int * len(devs))(*devs)
+        self.handle = lib.fftw_amd_slab_plan_dft_c2r(len(n), nn, len(devs), dv, _ptrs(ins), _ptrs(outs), flags)
+        if not self.handle:
+            raise ValueError("c2r slab planner returned NULL (invalid or unsupported problem)")
+        self._keep = (ins, outs)
+
+
+def slab_block_transpose(dst, da, db, I, blocks, stream=None, nt=-1):
+    """fftw_amd_slab_block_transpose (internal, for tests and tools/perf): the transposing-exchange kernel by itself;
+    blocks = [(src, dst_off, A, B, sa, sb)] with src a device array; nt = 1 / 0 nontemporal accesses on / off, -1 the
+    launcher's rule; returns the launcher's status"""
+    desc = []
+    for src, doff, A, B, sa, sb in blocks:
+        desc += [ptr(src) or 0, doff, A, B, sa, sb]
+    arr = (C.c_longlong * len(desc))(*desc)
+    return lib.fftw_amd_slab_block_transpose(ptr(dst), da, db, I, len(blocks), arr, nt, stream)
 
 
 # ---- one long 1-D transform over the GPUs of this process (fftw3_amd/csrc/slab1d.c)

@@ -59,6 +59,21 @@ size_t fa_hip_max_pitch(int dev);               /* largest pitch (bytes) of a 2-
 int   fa_hip_slab_twiddle(double *p, long long rows, long long width, long long row_stride, long long c0,
                           long long n, int sign, const void *lo, const void *hi, int shift, void *stream);
 
+/* Transposing exchange of the TRANSPOSED slab layouts (slab.c, kernels_slab.hip): one launch on `stream` (a stream
+   of the device that owns dst) that copies, for every source k < nsrc <= FA_HIP_SLAB_TR_MAXSRC,
+       dst[dst_off + b * db + a * da + i] = src[a * sa + b * sb + i]      a < A, b < B, i < I
+   in 16-byte complex elements (sources on peers are read through peer access).  I < 8 goes through an LDS tile
+   transposition, I >= 8 is copied directly.  nt: 1 / 0 nontemporal accesses on / off, -1 the library's policy (off unless
+   FFTW_AMD_NT=2 and every run is at least 128 bytes long).
+   Returns 0 when launched (or when there is nothing to move), 1 on arguments it cannot run. */
+#define FA_HIP_SLAB_TR_MAXSRC 32
+typedef struct {
+    const void *src;
+    long long dst_off, A, B, sa, sb;
+} fa_slab_tr_src;
+int   fa_hip_slab_transpose(void *dst, long long da, long long db, long long I, int nsrc,
+                            const fa_slab_tr_src *src, int nt, void *stream);
+
 /* Launch one step.  bufs[i] is the device base pointer of buffer id i, tables[i]
    the device pointer of table id i.  (chunk_start, chunk_n) select the slice
    of the batch loop when desc->batch_dim >= 0.  Returns 0 on success. */

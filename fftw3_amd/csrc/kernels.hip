@@ -1130,7 +1130,9 @@ extern "C" void *fa_hip_stream_create(void) {
 extern "C" void fa_hip_stream_destroy(void *s) { FA_CHECK(hipStreamDestroy((hipStream_t)s)); }
 extern "C" int fa_hip_get_device(void) { int d = 0; FA_CHECK(hipGetDevice(&d)); return d; }
 extern "C" void fa_hip_set_device(int dev) { FA_CHECK(hipSetDevice(dev)); }
-/* 0 on success; a missing peer path is not an error (hipMemcpyPeerAsync stages through the host then) */
+/* 0 when dev may address peer's memory, 1 when there is no peer path.  The batch-sharding layer ignores a missing
+   path (hipMemcpyPeerAsync stages through the host then); the slab planners return NULL for it, because their
+   exchanges read the peer's memory directly */
 extern "C" int fa_hip_enable_peer(int dev, int peer) {
     int can = 0, cur = 0;
     if (dev == peer) return 0;

@@ -134,6 +134,73 @@ int  fftw_amd_slab_num_devices(const fftw_amd_slab_plan p);
 fftw_plan fftw_amd_slab_local_plan(const fftw_amd_slab_plan p, int g, int which);   /* 0: rows plan, 1: column-block plan */
 void fftw_amd_destroy_slab_plan(fftw_amd_slab_plan p);
 
+/* ---- real data and the TRANSPOSED layouts of the slab plans (fftw3_amd/csrc/slab.c) ------------------------------
+   fftw_mpi_local_size_2d / _3d_transposed, fftw_mpi_plan_dft_r2c_2d / _3d, fftw_mpi_plan_dft_c2r_2d / _3d and
+   FFTW_MPI_TRANSPOSED_IN / _OUT of fftw/mpi/fftw3-mpi.h, devices of this process in the place of MPI ranks.  The
+   results are ordinary fftw_amd_slab_plans (execute / sync / num_devices / local_plan / destroy as above).
+
+   Sizes.  n is the LOGICAL size.  For real data nc = n[rank-1] / 2 + 1 and the complex array has the dimensions
+   n[0] x nc (rank 2) or n[0] x n[1] x nc (rank 3); the real array has the same rows with 2 nc doubles each (FFTW's
+   padded layout: the last 2 nc - n[rank-1] doubles of a row are padding).  Write n0 for n[0], n1' for the second
+   complex dimension (n[1]; nc for rank-2 real data) and rest for the product of the complex dimensions after the
+   second (1 for rank 2; n[2], or nc for real data, for rank 3).  Blocks by the block rule on n0 and on n1'.
+
+   Layouts of device g:
+   - normal:      [local_n0(g)][n1'][rest] complex; real: [local_n0(g)][n1] (x [n2]) with the padded last dimension.
+   - transposed:  [local_n1(g)][n0][rest] complex, local_n1 / local_1_start the block of n1'.  Element (c, j, i) is
+                  X[j][local_1_start + c][i].
+   fftw_amd_slab_local_size_transposed takes the COMPLEX dimensions (the caller passes nc as the last one for real
+   data, exactly as with fftw3-mpi) and returns max(local_n0 n1' rest, local_n1 n0 rest), the number of complex
+   elements device g must allocate for either array of a plan with a TRANSPOSED bit (a real array: twice as many
+   doubles).
+
+   Plans.  fftw_amd_slab_plan_dft accepts the two bits in `flags`: TRANSPOSED_OUT leaves the result in the transposed
+   layout, TRANSPOSED_IN expects the input in it; without them it plans and runs as before.  r2c (forward) accepts
+   TRANSPOSED_OUT only, c2r (backward, unnormalised) TRANSPOSED_IN only, and c2r may overwrite its complex input.
+   (void *)in[g] == (void *)out[g] is allowed everywhere.  Forward TRANSPOSED_OUT followed by backward TRANSPOSED_IN
+   returns N x with two exchanges instead of four.
+
+   Pipelines.  Normal order, real: the local r2c over the trailing dimension(s) first (c2r: last), the exchange /
+   columns / exchange-back of the c2c plan on the complex shape in between.  TRANSPOSED_OUT: trailing-dimension plan
+   in[g] -> W[g] (owned), ONE transposing exchange (device r pulls the block [local_n0(g)][local_n1(r)][rest] of
+   every W[g] into out[r][c][local_0_start(g) + j][:], kernels_slab.hip), length-n0 plan in place in out[r] -- for
+   rank 2 over contiguous rows.  TRANSPOSED_IN: the mirror image (length-n0 plan in[g] -> W[g], transposing exchange
+   into out[g], trailing plan in place).  Both bits: length-n0 plan, exchange, trailing plan, exchange.
+   fftw_amd_slab_local_plan(p, g, 0) is the trailing-dimension plan, (p, g, 1) the length-n0 plan.
+
+   NULL (never a failure inside execute): bad arguments or flag combinations, rank other than 2 / 3, an extent < 1,
+   a NULL array of a non-empty block, a named device that does not exist, distinct devices without peer access, a
+   local plan / buffer that cannot be made.  Planning works without a device. */
+#define FFTW_AMD_SLAB_TRANSPOSED_IN  (1U << 29)   /* same bits as FFTW_MPI_TRANSPOSED_IN / _OUT */
+#define FFTW_AMD_SLAB_TRANSPOSED_OUT (1U << 30)
+long long fftw_amd_slab_local_size_transposed(int rank, const long long *n, int ndev, int g,
+                                              long long *local_n0, long long *local_0_start,
+                                              long long *local_n1, long long *local_1_start);
+fftw_amd_slab_plan fftw_amd_slab_plan_dft_r2c(int rank, const long long *n, int ndev, const int *devs,
+                                              double *const *in, fftw_complex *const *out, unsigned flags);
+fftw_amd_slab_plan fftw_amd_slab_plan_dft_c2r(int rank, const long long *n, int ndev, const int *devs,
+                                              fftw_complex *const *in, double *const *out, unsigned flags);
+/* The block moves of exchange `which` (0, 1: in execution order) exactly as the executor iterates them, 13 values
+   each: source buffer (0 in, 1 out, 2 the plan's W), source device index, source element offset, destination
+   buffer, destination device index, destination element offset, extents A, B, I, source strides of a and b,
+   destination strides of a and b -- in complex elements:
+       dst[doff + a dsa + b dsb + i] = src[soff + a ssa + b ssb + i],   a < A, b < B, i < I.
+   Normal-order exchanges are 2-D copies (B = 1); transposing ones run as one kernel launch per destination device.
+   Returns the number of moves (ops holds at most cap of them), -1 for a bad plan / exchange, 0 for a 1-D plan. */
+#define FFTW_AMD_SLAB_OP_LEN 13
+int fftw_amd_slab_exchange_ops(const fftw_amd_slab_plan p, int which, long long *ops, int cap);
+/* fftw_amd_slab_execute between device events: waits for the plan's streams, records an event on every device's
+   stream, executes, records again, synchronises; *ms = the longest event-to-event time of any device's stream.  For
+   measurements (tools/perf); 0 on success, -1 for a bad or 1-D plan or without a device. */
+int fftw_amd_slab_execute_timed(fftw_amd_slab_plan p, double *ms);
+/* INTERNAL, for the tests and tools/perf only -- not part of the interface a caller should build on.  The
+   transposing-exchange kernel by itself: nsrc blocks, 6 values each in desc (source device pointer, destination
+   element offset, A, B, source strides of a and b), dst[off + b db + a da + i] = src[a sa + b sb + i]; enqueued on
+   `stream` of the current device.  nt: 1 / 0 nontemporal accesses on / off, -1 the launcher's own rule (what the
+   plans use).  0 when launched, 1 on arguments it cannot run, -1 without a device. */
+int fftw_amd_slab_block_transpose(fftw_complex *dst, long long da, long long db, long long I, int nsrc,
+                                  const long long *desc, int nt, void *stream);
+
 /* ---- one long 1-D transform spread over the GPUs of a node (fftw3_amd/csrc/slab1d.c) -----------------------------
    The reference's distributed 1-D solver (fftw/mpi/dft-rank1.c; fftw_mpi_local_size_1d / fftw_mpi_plan_dft_1d of
    fftw/mpi/fftw3-mpi.h:97-138), devices of this process in the place of MPI ranks.  The result is an ordinary
