@@ -293,55 +293,54 @@ def ref_numpy(case, x):
     return _np_r2r(x, case.r2r)
 
 
+class Guards(object):
+    """what the arenas around run_gpu's device arrays saw (tests/footprint.py): violations, one entry per arena, of
+    "every word outside the output footprint is bit-identical", and whether the input of an out-of-place plan came
+    back bit for bit (None: in place, or a slab plan, which has its own tests)"""
+    def __init__(self, violations=(), preserved=None):
+        self.violations, self.preserved = list(violations), preserved
+
+
+def _problem(case):
+    import footprint as F
+    n, hm = case.n, case.hm
+    kw = dict(sign=case.sign)
+    if case.kind == "c2c":
+        lay = F.Layout(None, hm, 1) if case.col else F.Layout()
+        return F.Problem("c2c", case.shape, hm, lay, lay, **kw)
+    if case.kind == "r2c" and case.padded:
+        h = n // 2 + 1
+        return F.Problem("r2c", (n,), hm, F.Layout((2 * h,), 1, 2 * h), F.Layout(None, 1, h), inplace=True)
+    if case.kind == "r2r":
+        kw["r2r"] = [case.r2r]
+    return F.Problem(case.kind, (n,), hm, F.Layout(), F.Layout(), **kw)
+
+
 def run_gpu(case, x):
-    """execute the case's plan on cuda:0; returns (output in the logical layout of the reference, sprint)"""
+    """execute the case's plan on cuda:0, its device arrays inside NaN-patterned arenas (tests/footprint.py);
+    returns (output in the logical layout of the reference, sprint, Guards)"""
     import torch
     import fftw3_amd as fa
+    import footprint as F
     n, hm, dev = case.n, case.hm, torch.device("cuda:0")
     with knobs(case.env):
-        if case.kind == "c2c":
-            st, dist = (hm, 1) if case.col else (1, n)
-            flat = np.ascontiguousarray(x.reshape(hm, n).T if case.col else x.reshape(hm, n)).reshape(-1)
-            xd = torch.from_numpy(flat).to(dev)
-            yd = torch.zeros_like(xd)
-            p = fa.plan_many_dft(len(case.shape), list(case.shape), hm, xd, None, st, dist, yd, None, st, dist,
-                                 case.sign)
+        if case.kind != "slab":
+            prob = _problem(case)
+            AR = prob.arenas()
+            prob.scatter(AR, x)
+            full = [a.to_device(dev) for a in AR]
+            ref = [t.clone() for t in full]
+            p = prob.plan(fa, [t[a.lo:] for t, a in zip(full, AR)])
             p.execute()
             p.sync()
-            y = yd.cpu().numpy().reshape(n, hm).T if case.col else yd.cpu().numpy()
-            return y.reshape(x.shape), p.sprint()
-        if case.kind == "r2c":
-            h = n // 2 + 1
-            if case.padded:
-                buf = np.zeros((hm, 2 * h))
-                buf[:, :n] = x
-                bd = torch.from_numpy(buf).to(dev)
-                cv = bd.view(-1).view(torch.complex128)
-                p = fa.plan_many_dft_r2c(1, [n], hm, bd, None, 1, 2 * h, cv, None, 1, h)
-                p.execute()
-                p.sync()
-                return cv.cpu().numpy().reshape(hm, h), p.sprint()
-            xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-            yd = torch.zeros((hm, h), dtype=torch.complex128, device=dev)
-            p = fa.plan_many_dft_r2c(1, [n], hm, xd, None, 1, n, yd, None, 1, h)
-            p.execute()
-            p.sync()
-            return yd.cpu().numpy(), p.sprint()
-        if case.kind == "c2r":
-            h = n // 2 + 1
-            xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-            yd = torch.zeros((hm, n), dtype=torch.float64, device=dev)
-            p = fa.plan_many_dft_c2r(1, [n], hm, xd, None, 1, h, yd, None, 1, n)
-            p.execute()
-            p.sync()
-            return yd.cpu().numpy(), p.sprint()
-        if case.kind == "r2r":
-            xd = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-            yd = torch.zeros_like(xd)
-            p = fa.plan_many_r2r(1, [n], hm, xd, None, 1, n, yd, None, 1, n, [case.r2r])
-            p.execute()
-            p.sync()
-            return yd.cpu().numpy(), p.sprint()
+            torch.cuda.synchronize()
+            viol = [F.check(r, t, w) for r, t, w in zip(ref, full, prob.written(AR))]
+            kept = None if prob.inplace else F.same_bits(full[0], ref[0])
+            out = full[-1][AR[-1].lo:AR[-1].lo + AR[-1].span].cpu().numpy()
+            y = prob.gather([out])
+            if case.kind == "c2c":
+                y = y.reshape(x.shape)
+            return y, p.sprint(), Guards(viol, kept)
         assert case.kind == "slab" and hm == 1
         xd = torch.from_numpy(np.ascontiguousarray(x.reshape(-1))).to(dev)
         yd = torch.zeros_like(xd)
@@ -352,7 +351,7 @@ def run_gpu(case, x):
         sp.sync()
         y = yd.cpu().numpy().reshape(x.shape)
         sp.destroy()
-        return y, s
+        return y, s, Guards()
 
 
 def measure(case, got, x):

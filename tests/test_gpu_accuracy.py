@@ -5,7 +5,9 @@ reference, and
     e_gpu <= 3 * max(e_oracle, e_numpy, u / 2)
 
 for the whole batch and, for n >= 1024, for every batch entry on its own (an error confined to a ragged last tile or
-one chunk is not diluted by the rest).  Every case also asserts the kernel its plan's sprint() shows.  This is in
+one chunk is not diluted by the rest).  Every case also asserts the kernel its plan's sprint() shows, and its device
+arrays sit in the NaN-patterned arenas of tests/footprint.py: no word outside the output footprint may change and the
+input of an out-of-place plan must come back bit for bit.  This is in
 addition to the 1e-10 checks of the other modules, which only see indexing bugs: a twiddle off by a few ulp passes
 those and fails this.  The slowest cases carry "slow" in their ids (-k slow selects them)."""
 import numpy as np
@@ -23,8 +25,10 @@ CASES = AC.cases()
 @pytest.mark.parametrize("case", CASES, ids=[("slow-" if c.slow else "") + c.id for c in CASES])
 def test_rms_error_within_three_times_the_references(case):
     x = AC.make_input(case)
-    got, sprint = AC.run_gpu(case, x)
+    got, sprint, guards = AC.run_gpu(case, x)
     AC.check_labels(case, sprint)
+    assert not any(guards.violations), (case.id, guards.violations, sprint)
+    assert guards.preserved is not False, (case.id, "the input of an out-of-place plan changed", sprint)
     m = AC.measure(case, got, x)
     ratio = m["gpu"] / max(m["oracle"], m["numpy"], A.U / 2)
     print("%s gpu %.3f u oracle %.3f u numpy %.3f u ratio %.2f" % (case.id, m["gpu"] / A.U, m["oracle"] / A.U,

@@ -1,0 +1,64 @@
+"""The footprint contract on the GPU (tests/footprint.py): every case of tests/footprint_cases.py
+executes its plan twice on arenas whose every non-input word is a distinct quiet NaN, and
+
+  1. no word outside FFTW's output footprint changes (guards, stride gaps, padding, spare columns, the input),
+  2. the values inside it pass the rms gate of tests/accuracy.py against the long-double reference -- the gaps are
+     NaN, so one over-read that reaches the result fails it,
+  3. a second execute() of the same plan, the arenas re-initialised, leaves bit-identical output arenas,
+  4. the input arenas of an out-of-place plan are bit-identical after both, for every kind and whatever the flags.
+
+Every case prints the kernels its plan's sprint() shows; dense cases assert the labels the accuracy matrix pins."""
+import numpy as np
+import pytest
+
+import accuracy as A
+import accuracy_cases as AC
+import footprint_cases as FC
+
+A.require_longdouble()
+pytestmark = pytest.mark.gpu
+
+CASES = FC.cases()
+
+
+PASSED = {}          # id -> sprint of the cases that ran and met the whole pass condition in this session
+
+
+def _run_and_check(case):
+    x = FC.make_input(case)
+    r = FC.run(case, x)
+    print("%s :: %s" % (case.id, " | ".join(ln.strip() for ln in r.sprint.strip().split("\n")[1:])))
+    AC.check_labels(case, r.sprint)
+    assert not any(r.violations), (case.id, r.violations, r.sprint)
+    m = FC.measure(case, r.got, x)
+    print("  gpu %.3f u oracle %.3f u numpy %.3f u" % (m["gpu"] / A.U, m["oracle"] / A.U, m["numpy"] / A.U))
+    assert A.passes(m["gpu"], m["oracle"], m["numpy"]), (case.id, m["gpu"] / A.U, m["oracle"] / A.U,
+                                                        m["numpy"] / A.U, r.sprint)
+    if "per" in m:
+        eg, eo, en = m["per"]
+        for b in range(case.hm):
+            assert A.passes(eg[b], eo[b], en[b]), (case.id, "entry %d" % b, eg[b] / A.U, eo[b] / A.U, en[b] / A.U)
+    assert r.repeat, (case.id, "the second execution of the plan differs from the first", r.sprint)
+    assert r.preserved is not False, (case.id, "the input of an out-of-place plan changed", r.sprint)
+    PASSED[case.id] = r.sprint
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_plan_writes_only_its_footprint(case):
+    _run_and_check(case)
+
+
+def test_every_c2c_family_is_reached_by_a_non_dense_case_that_passed():
+    """every kernel family of the c2c table shows in the sprint() of a non-dense case that executed and met the pass
+    condition.  After the parametrised test above that is a lookup; selected on its own, this test runs the gapped
+    and in-place cases itself."""
+    def sprint_of(c):
+        if c.id not in PASSED and not PASSED_ANY[0] and c.layout in ("gapped", "dense-inplace") and c.sign < 0:
+            _run_and_check(c)
+        return PASSED.get(c.id)
+
+    PASSED_ANY = [bool(PASSED)]
+    reached = FC.family_labels(sprint_of)
+    for f, cid in sorted(reached.items()):
+        print("%-24s %s" % (f, cid))
+    assert sorted(reached) == sorted(FC.FAMILIES), sorted(set(FC.FAMILIES) - set(reached))

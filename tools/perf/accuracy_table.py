@@ -33,7 +33,7 @@ def main():
         if (a.family and c.fam != a.family) or (a.skip_slow and c.slow):
             continue
         x = AC.make_input(c)
-        got, s = AC.run_gpu(c, x)
+        got, s, _ = AC.run_gpu(c, x)
         AC.check_labels(c, s)
         m = AC.measure(c, got, x)
         r = m["gpu"] / max(m["oracle"], m["numpy"], A.U / 2)
