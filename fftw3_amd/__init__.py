@@ -204,6 +204,7 @@ _sig("fftw_amd_plan_workspace_bytes", C.c_size_t, _vp)
 _sig("fftw_amd_set_chunk_bytes", None, C.c_size_t)
 _sig("fftw_amd_plan_paired", C.c_int, _vp)
 _sig("fftw_amd_plan_lanes", C.c_int, _vp)
+_sig("fftw_amd_p1024_launches", None, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
 _sig("fftw_amd_set_device", C.c_int, C.c_int)
 _sig("fftw_amd_get_device", C.c_int)
 _sig("fftw_amd_plan_num_steps", C.c_int, _vp)
@@ -222,6 +223,13 @@ _libc_free.argtypes = [_vp]
 
 def device_count():
     return lib.fftw_amd_device_count()
+
+
+def p1024_launches():
+    """(full, general): launches of the 1024-point register pass so far in this process, by kernel form"""
+    full, general = C.c_longlong(), C.c_longlong()
+    lib.fftw_amd_p1024_launches(C.byref(full), C.byref(general))
+    return full.value, general.value
 
 
 def ptr(x):

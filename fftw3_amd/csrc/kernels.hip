@@ -1212,6 +1212,38 @@ static int fill_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *co
     return 0;
 }
 
+/* launches of the two forms of the 1024-point pass since the library was loaded (fftw_amd_p1024_launches) */
+static std::atomic<long long> g_p1024_full{0}, g_p1024_general{0};
+
+extern "C" void fftw_amd_p1024_launches(long long *full, long long *general) {
+    if (full) *full = g_p1024_full.load();
+    if (general) *general = g_p1024_general.load();
+}
+
+/* The full-tile form (pass1024_full_kernel) applies when every tile of the launch holds 8 sequences, the step asks
+   for nothing but a cache policy and (at most) the input twiddle, and an element's byte offset inside its tile fits
+   31 bits on either side. */
+static bool p1024_full_ok(const P1024Args &pa, int tw) {
+    if (tw == 1 || pa.lo_sh != 0 || pa.dn[0] % 8 != 0) return false;
+    if (pa.flags & ~(FFTW_AMD_F_NT_IN | FFTW_AMD_F_NT_OUT | FFTW_AMD_F_TW_IN)) return false;
+    const i64 lim = 0x7fffffffLL / 8 - 2;      /* in doubles */
+    /* negative strides, and offsets that do not fit, keep the general kernel */
+    if (pa.is_l <= 0 || pa.os_l <= 0 || pa.dis[0] < 0 || pa.dos[0] < 0) return false;
+    if (pa.is_l > lim / 1023 || pa.os_l > lim / 1023 || pa.dis[0] > lim / 7 || pa.dos[0] > lim / 7) return false;   /* no overflow below */
+    if (1023 * pa.is_l + 7 * pa.dis[0] > lim || 1023 * pa.os_l + 7 * pa.dos[0] > lim) return false;
+    return true;
+}
+
+template <bool IN_T, bool OUT_T, int HAS_TW>
+static void launch_p1024_full(const P1024Args &pa, dim3 grid, hipStream_t st) {
+    const size_t lds = FA_P1024_LDS_DOUBLES * sizeof(double);
+    const bool nti = (pa.flags & FFTW_AMD_F_NT_IN) != 0, nto = (pa.flags & FFTW_AMD_F_NT_OUT) != 0;
+    if (nti && nto) fa_launch_lds<pass1024_full_kernel<IN_T, OUT_T, HAS_TW, true, true>>(grid, dim3(256), lds, lds, st, pa);
+    else if (nti) fa_launch_lds<pass1024_full_kernel<IN_T, OUT_T, HAS_TW, true, false>>(grid, dim3(256), lds, lds, st, pa);
+    else if (nto) fa_launch_lds<pass1024_full_kernel<IN_T, OUT_T, HAS_TW, false, true>>(grid, dim3(256), lds, lds, st, pa);
+    else fa_launch_lds<pass1024_full_kernel<IN_T, OUT_T, HAS_TW, false, false>>(grid, dim3(256), lds, lds, st, pa);
+}
+
 static int launch_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables,
                         i64 cs, i64 cn, hipStream_t st) {
     P1024Args pa;
@@ -1221,7 +1253,15 @@ static int launch_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *
     if (fill_p1024(d, bufs, tables, cs, cn, pa, &nblocks, &in_t, &out_t, &tw)) return 1;
     if (nblocks <= 0) return 0;
     const dim3 grid((unsigned)nblocks, 1, 1);
-#define FA_P1024_CASE(I, O, W) if (in_t == I && out_t == O && tw == W) { launch_p1024_variant<I, O, W>(pa, grid, st); return 0; }
+    if (p1024_full_ok(pa, tw)) {
+#define FA_P1024_FULL(I, O, W) if (in_t == I && out_t == O && tw == W) { g_p1024_full.fetch_add(1); launch_p1024_full<I, O, W>(pa, grid, st); return 0; }
+        FA_P1024_FULL(true, true, 0)   FA_P1024_FULL(true, true, 2)
+        FA_P1024_FULL(false, true, 0)  FA_P1024_FULL(false, true, 2)
+        FA_P1024_FULL(true, false, 0)  FA_P1024_FULL(true, false, 2)
+        FA_P1024_FULL(false, false, 0) FA_P1024_FULL(false, false, 2)
+#undef FA_P1024_FULL
+    }
+#define FA_P1024_CASE(I, O, W) if (in_t == I && out_t == O && tw == W) { g_p1024_general.fetch_add(1); launch_p1024_variant<I, O, W>(pa, grid, st); return 0; }
     FA_P1024_CASE(true, true, 0)  FA_P1024_CASE(true, true, 1)  FA_P1024_CASE(true, true, 2)
     FA_P1024_CASE(false, true, 0) FA_P1024_CASE(false, true, 1) FA_P1024_CASE(false, true, 2)
     FA_P1024_CASE(true, false, 0) FA_P1024_CASE(true, false, 1) FA_P1024_CASE(true, false, 2)
@@ -1292,6 +1332,7 @@ extern "C" int fa_hip_launch_pair1024(const fftw_amd_step_desc *d_second, double
     if (n1 + n2 <= 0) return 0;
     if (n1 + n2 > 0x7fffffffLL) return 1;
     const size_t lds = FA_P1024_LDS_DOUBLES * sizeof(double);
+    g_p1024_general.fetch_add(1);
     fa_launch_lds<pass1024_pair_kernel>(dim3((unsigned)(n1 + n2)), dim3(256), lds, lds, (hipStream_t)stream,
                                         a2, a1, (unsigned)n2, (unsigned)n1);
     hipError_t e = hipGetLastError();

@@ -51,8 +51,23 @@ template <int M> struct W32 {
     static constexpr double s = cs[(M + 24) & 31];
 };
 
-/* v * conj(w32^M) with the trivial cases folded at compile time */
+/* The twiddle products of this pass (the butterfly's constants, table combinations, the product trees and their
+   application), with the rounding fixed in source: one rounded product and one FMA per component, always the same
+   one.  Left to the compiler's contraction of c_mul / c_mulc, two instantiations of the same source fuse the other
+   product in some places, and the general and the full-tile kernel differ in the last bits of the same sequence
+   (tools/perf/isa_fp64_shapes.py shows where). */
+FA_DEV cplx tw_mul(cplx a, cplx w) {
+#pragma clang fp contract(off)
+    return c_make(__builtin_fma(a.x, w.x, -(a.y * w.y)), __builtin_fma(a.x, w.y, a.y * w.x));
+}
+FA_DEV cplx tw_mulc(cplx a, cplx w) {
+#pragma clang fp contract(off)
+    return c_make(__builtin_fma(a.x, w.x, a.y * w.y), __builtin_fma(a.y, w.x, -(a.x * w.y)));
+}
+
+/* v * conj(w32^M) with the trivial cases folded at compile time; no contraction with the caller's sums either */
 template <int M> FA_DEV cplx mul_w32c(cplx v) {
+#pragma clang fp contract(off)
     if constexpr ((M & 31) == 0) return v;
     else if constexpr ((M & 31) == 8) return c_mni(v);
     else if constexpr ((M & 31) == 16) return c_make(-v.x, -v.y);
@@ -61,7 +76,7 @@ template <int M> FA_DEV cplx mul_w32c(cplx v) {
     else if constexpr ((M & 31) == 12) return c_make((v.y - v.x) * FA_SQRT1_2, -(v.x + v.y) * FA_SQRT1_2);
     else if constexpr ((M & 31) == 20) return c_make(-(v.x + v.y) * FA_SQRT1_2, (v.x - v.y) * FA_SQRT1_2);
     else if constexpr ((M & 31) == 28) return c_make((v.x - v.y) * FA_SQRT1_2, (v.x + v.y) * FA_SQRT1_2);
-    else return c_mulc(v, c_make(W32<M>::c, W32<M>::s));
+    else return tw_mulc(v, c_make(W32<M>::c, W32<M>::s));
 }
 
 /* slot of logical output k after bfly32: k = k2 + 8 k1  ->  k1 + 4 k2 */
@@ -104,7 +119,7 @@ FA_DEV void bfly32(cplx *x) {
 template <int BIT, int D, bool HAVE, bool PERM> struct TwTree {
     static FA_DEV void run(cplx *x, const cplx *pw, cplx acc) {
         TwTree<BIT - 1, D, HAVE, PERM>::run(x, pw, acc);
-        cplx nxt = HAVE ? c_mul(acc, pw[BIT]) : pw[BIT];
+        cplx nxt = HAVE ? tw_mul(acc, pw[BIT]) : pw[BIT];
         TwTree<BIT - 1, D + (1 << BIT), true, PERM>::run(x, pw, nxt);
     }
 };
@@ -112,7 +127,7 @@ template <int BIT, int D, bool HAVE, bool PERM> struct TwTree {
 template <int D, bool HAVE, bool PERM> struct TwTree<-1, D, HAVE, PERM> {
     static FA_DEV void run(cplx *x, const cplx *, cplx acc) {
         constexpr int S = PERM ? slot32(D) : D;
-        if (HAVE) x[S] = c_mulc(x[S], acc);
+        if (HAVE) x[S] = tw_mulc(x[S], acc);
     }
 };
 
@@ -125,6 +140,23 @@ template <bool IN_T, bool OUT_T> FA_DEV int lds_index(int d, int a, int t) {
 }
 
 #define FA_P1024_LDS_DOUBLES 8448
+
+/* exchange through LDS, one real plane at a time: item (ai, ti) gives Y_ai[d] = x[slot32(d)], item (dq, to) gets
+   y[q] = Y_q[dq].  All 256 work-items call. */
+template <bool IN_T, bool OUT_T>
+FA_DEV void p1024_exchange(const cplx *x, cplx *y, double *plane, int ai, int ti, int dq, int to) {
+#pragma unroll
+    for (int d = 0; d < 32; ++d) plane[lds_index<IN_T, OUT_T>(d, ai, ti)] = x[slot32(d)].x;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 32; ++q) y[q].x = plane[lds_index<IN_T, OUT_T>(dq, q, to)];
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < 32; ++d) plane[lds_index<IN_T, OUT_T>(d, ai, ti)] = x[slot32(d)].y;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 32; ++q) y[q].y = plane[lds_index<IN_T, OUT_T>(dq, q, to)];
+}
 
 /* one tile = 8 sequences of 1024; pointers already address the tile origin */
 struct P1024Tile {
@@ -207,10 +239,10 @@ FA_DEV void p1024_tile(const P1024Tile &a, double *plane, const int tid) {
 
     /* ---- inter-pass twiddle on the input: conj(w_N^((ai + 32 i) q)) */
     if (HAS_TW == 2 && !(ABL & 2)) {
-        cplx base = c_mul(twl[5], twh[5]);
+        cplx base = tw_mul(twl[5], twh[5]);
         cplx pw[5];
 #pragma unroll
-        for (int s = 0; s < 5; ++s) pw[s] = c_mul(twl[s], twh[s]);
+        for (int s = 0; s < 5; ++s) pw[s] = tw_mul(twl[s], twh[s]);
         TwTree<4, 0, true, false>::run(x, pw, base);
     }
 
@@ -224,17 +256,7 @@ FA_DEV void p1024_tile(const P1024Tile &a, double *plane, const int tid) {
 #pragma unroll
         for (int q = 0; q < 32; ++q) y[q] = x[slot32(q)];
     } else {
-#pragma unroll
-    for (int d = 0; d < 32; ++d) plane[lds_index<IN_T, OUT_T>(d, ai, ti)] = x[slot32(d)].x;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 32; ++q) y[q].x = plane[lds_index<IN_T, OUT_T>(dq, q, to)];
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < 32; ++d) plane[lds_index<IN_T, OUT_T>(d, ai, ti)] = x[slot32(d)].y;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 32; ++q) y[q].y = plane[lds_index<IN_T, OUT_T>(dq, q, to)];
+    p1024_exchange<IN_T, OUT_T>(x, y, plane, ai, ti, dq, to);
     }
 
     /* ---- second radix-32 butterfly over a: X[dq + 32 c] in y[slot32(c)] */
@@ -242,10 +264,10 @@ FA_DEV void p1024_tile(const P1024Tile &a, double *plane, const int tid) {
 
     /* ---- inter-pass twiddle conj(w_N^((dq + 32 c) q)), q = position of this sequence */
     if (HAS_TW == 1 && !(ABL & 2)) {
-        cplx base = c_mul(twl[5], twh[5]);
+        cplx base = tw_mul(twl[5], twh[5]);
         cplx pw[5];
 #pragma unroll
-        for (int s = 0; s < 5; ++s) pw[s] = c_mul(twl[s], twh[s]);
+        for (int s = 0; s < 5; ++s) pw[s] = tw_mul(twl[s], twh[s]);
         TwTree<4, 0, true, true>::run(y, pw, base);
     }
 
@@ -295,6 +317,24 @@ struct P1024Args {
     long long *dbg;
 };
 
+/* this workgroup's tile of dim 0 and its offsets along the other loop dims; returns its place in the tile order */
+FA_DEV unsigned p1024_block_origin(const P1024Args &a, unsigned &tile, i64 &soff, i64 &doff, i64 &twb) {
+    unsigned blk = (unsigned)fa_xcd_remap((i64)blockIdx.x, (i64)gridDim.x);
+    const unsigned nt = (unsigned)a.ntiles;
+    tile = blk % nt;
+    unsigned rest = blk / nt;
+    soff = 0; doff = 0; twb = 0;
+    for (int d = 1; d < a.ndims; ++d) {
+        const unsigned dn = (unsigned)a.dn[d];
+        unsigned idx = rest % dn;
+        rest /= dn;
+        soff += (i64)idx * a.dis[d];
+        doff += (i64)idx * a.dos[d];
+        twb += (i64)idx * a.dtw[d];
+    }
+    return blk;
+}
+
 template <bool IN_T, bool OUT_T, int HAS_TW, int ABL = 0>
 __global__ void __launch_bounds__(256, 2)
 pass1024_kernel(const P1024Args a) {
@@ -307,19 +347,9 @@ pass1024_kernel(const P1024Args a) {
     /* the launcher keeps the grid below 2^31 blocks: 32-bit index arithmetic (a 64-bit
        division is ~130 instructions on this ISA, and this prologue is on every workgroup's
        critical path before its first load) */
-    unsigned blk = (unsigned)fa_xcd_remap((i64)blockIdx.x, (i64)gridDim.x);
-    const unsigned nt = (unsigned)a.ntiles;
-    unsigned tile = blk % nt;
-    unsigned rest = blk / nt;
-    i64 soff = 0, doff = 0, twb = 0;
-    for (int d = 1; d < a.ndims; ++d) {
-        const unsigned dn = (unsigned)a.dn[d];
-        unsigned idx = rest % dn;
-        rest /= dn;
-        soff += (i64)idx * a.dis[d];
-        doff += (i64)idx * a.dos[d];
-        twb += (i64)idx * a.dtw[d];
-    }
+    unsigned tile;
+    i64 soff, doff, twb;
+    const unsigned blk = p1024_block_origin(a, tile, soff, doff, twb);
     const i64 t0 = (i64)tile * (8 >> a.lo_sh);
     P1024Tile t;
     t.lo_sh = a.lo_sh; t.lo_is = a.lo_is; t.lo_os = a.lo_os;
@@ -344,6 +374,88 @@ pass1024_kernel(const P1024Args a) {
         }
     }
     p1024_tile<IN_T, OUT_T, HAS_TW, ABL>(t, plane, threadIdx.x);
+}
+
+/* ---- full-tile form: every sequence of every tile of the launch is present (dn[0] % 8 == 0, no inner tile dim),
+   the cache policy of each side is a template parameter and neither side swaps re / im.  Same tile shape, LDS
+   exchange, butterflies and load order as p1024_tile; what is gone is work a full tile never needs:
+     - the selects between loaded data and the zero fill of absent sequences, and the tests of `flags`;
+     - the 64-bit vector address of every row: an element's offset inside its tile is 32 bits (one VALU add per
+       row), the tile's origin stays in scalar registers.
+   The twiddles are generated exactly as in p1024_tile, with the same fixed-rounding products (tw_mul / tw_mulc), so
+   both forms give the same bits for the same sequence. */
+
+/* HAS_TW is 0 or 2.  src / dst / q0 are the tile's origin and the twiddle position of its first sequence, all
+   uniform over the workgroup.  The launcher guarantees 0 <= 8 (1023 is_l + 7 dis[0]) < 2^31, the same on the
+   destination side (an element's byte offset inside its tile is a 32-bit number, added to a scalar base). */
+template <bool IN_T, bool OUT_T, int HAS_TW, bool NT_IN, bool NT_OUT>
+FA_DEV void p1024_tile_full(const P1024Args &a, const double *src, double *dst, const i64 q0, double *plane, const int tid) {
+    static_assert(HAS_TW == 0 || HAS_TW == 2, "the output twiddle keeps the general kernel");
+    const int ti = IN_T ? (tid & 7) : (tid >> 5);
+    const int ai = IN_T ? (tid >> 3) : (tid & 31);
+    const int to = OUT_T ? (tid & 7) : (tid >> 5);
+    const int dq = OUT_T ? (tid >> 3) : (tid & 31);
+
+    /* tables first: the vector-memory pipe returns loads in order (see p1024_tile) */
+    cplx pw1024[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) pw1024[s] = a.w1024[ai << s];
+    cplx twl[6], twh[6];
+    if (HAS_TW == 2) {
+        const i64 q = q0 + (i64)ti * a.dtw[0];
+        const i64 mask = (1LL << a.tw_shift) - 1;
+        const i64 m0 = q * ai;
+        twl[5] = a.tw_lo[m0 & mask]; twh[5] = a.tw_hi[m0 >> a.tw_shift];
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            const i64 m = (q * 32) << s;
+            twl[s] = a.tw_lo[m & mask]; twh[s] = a.tw_hi[m >> a.tw_shift];
+        }
+    }
+    cplx x[32];
+    {
+        /* byte offsets: a 32-bit vector offset on a scalar base is an addressing mode of the global loads */
+        const char *base_in = reinterpret_cast<const char *>(src);
+        const unsigned off = 8u * ((unsigned)ai * (unsigned)a.is_l + (unsigned)ti * (unsigned)a.dis[0]);
+        const unsigned step = 256u * (unsigned)a.is_l;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) x[i] = ld_cplx<NT_IN>(reinterpret_cast<const double *>(base_in + (off + i * step)));
+    }
+
+    if (HAS_TW == 2) {
+        cplx base = tw_mul(twl[5], twh[5]);
+        cplx pw[5];
+#pragma unroll
+        for (int s = 0; s < 5; ++s) pw[s] = tw_mul(twl[s], twh[s]);
+        TwTree<4, 0, true, false>::run(x, pw, base);
+    }
+    bfly32(x);
+    TwTree<4, 0, false, true>::run(x, pw1024, c_make(1.0, 0.0));
+
+    cplx y[32];
+    p1024_exchange<IN_T, OUT_T>(x, y, plane, ai, ti, dq, to);
+
+    bfly32(y);
+
+    {
+        char *base_out = reinterpret_cast<char *>(dst);
+        const unsigned off = 8u * ((unsigned)dq * (unsigned)a.os_l + (unsigned)to * (unsigned)a.dos[0]);
+        const unsigned step = 256u * (unsigned)a.os_l;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) st_cplx<NT_OUT>(reinterpret_cast<double *>(base_out + (off + c * step)), y[slot32(c)]);
+    }
+}
+
+template <bool IN_T, bool OUT_T, int HAS_TW, bool NT_IN, bool NT_OUT>
+__global__ void __launch_bounds__(256, 2)
+pass1024_full_kernel(const P1024Args a) {
+    extern __shared__ __attribute__((aligned(16))) double plane[];
+    unsigned tile;
+    i64 soff, doff, twb;
+    p1024_block_origin(a, tile, soff, doff, twb);
+    const i64 t0 = (i64)tile * 8;
+    p1024_tile_full<IN_T, OUT_T, HAS_TW, NT_IN, NT_OUT>(a, a.src + soff + t0 * a.dis[0], a.dst + doff + t0 * a.dos[0],
+                                                        twb + t0 * a.dtw[0], plane, threadIdx.x);
 }
 
 #endif /* FA_PASS1024_HPP */

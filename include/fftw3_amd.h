@@ -381,6 +381,12 @@ int fftw_amd_plan_paired(const fftw_plan p);
    launches above).  The lanes fork from and join the plan's stream (fftw_amd_plan_set_stream) inside every
    fftw_execute*.  1 for single-chunk, one-step and oversized-chunk plans.  Known once the plan is set up. */
 int fftw_amd_plan_lanes(const fftw_plan p);
+/* Launches of the register-resident 1024-point pass since the library was loaded, by form: `full` counts the
+   full-tile kernel (every tile of the launch holds 8 sequences, no re / im swap, no output twiddle), `general`
+   everything else, pair launches included.  Either pointer may be NULL.
+   DEBUG / INTROSPECTION ONLY: a hook for the test suite and profiling scripts, not part of the stable ABI; it may
+   change or go away without notice. */
+void fftw_amd_p1024_launches(long long *full, long long *general);
 /* host copy of table `id` as interleaved doubles; returns its length in
    doubles (writes at most cap doubles). */
 long long fftw_amd_plan_table(const fftw_plan p, int id, double *dst, long long cap);
