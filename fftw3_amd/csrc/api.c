@@ -108,6 +108,8 @@ static plan *clone_problem(const plan *p, fa_cfg c) {
     q->in_im = p->in_im; q->out_im = p->out_im;
     q->single_chunk = p->single_chunk;
     q->via_scratch = p->via_scratch;
+    q->tr_kind = p->tr_kind;
+    q->tr = p->tr;
     q->cfg = c;
     return q;
 }
@@ -296,6 +298,22 @@ static int inplace_same_locations(const plan *p) {
     return 1;
 }
 
+/* The caller's own loops (transform dims and howmany dims, extent-1 ones included, strides in doubles) as a
+   transposition (fa_match_transpose).  Rank-0 guru plans with exchanged strides are how FFTW callers transpose; an
+   extent-1 loop still says which side is which (a 1 x 40 matrix), so the match is made here, before such loops are
+   dropped. */
+static int match_user_loops(int rank, const fftw_iodim64 *dims, int hrank, const fftw_iodim64 *hdims,
+                            int mul_i, int mul_o, i64 unit, fa_transp *t) {
+    fa_dim l[2 * FA_MAXRANK];
+    int i, nl = 0;
+    for (i = 0; i < rank + hrank; ++i) {
+        const fftw_iodim64 *d = i < rank ? &dims[i] : &hdims[i - rank];
+        l[nl].n = d->n; l[nl].is = d->is * mul_i; l[nl].os = d->os * mul_o;
+        ++nl;
+    }
+    return fa_match_transpose(l, nl, unit, t);
+}
+
 /* move the loop with the largest stride to hdims[0]: it is the chunked batch */
 static void pick_batch(plan *p) {
     int i, best = 0;
@@ -354,11 +372,24 @@ static plan *mk_guru(int type, int rank, const fftw_iodim64 *dims, int hrank,
     pick_batch(p);
     p->in_im = (type == FA_R2C) ? 0 : (i64)(ii - ri);
     p->out_im = (type == FA_C2R) ? 0 : (i64)(io - ro);
+    if (type == FA_C2C && ii - ri == 1 && io - ro == 1 && !((size_t)ri % 16) && !((size_t)ro % 16)) {
+        /* aligned interleaved arrays: transpositions run on the tile kernels (planner.c emit_transpose).  Rank 0 with
+           two arrays: one tiled step.  One array, square: the in-place step -- alone for rank 0, after the ordinary
+           in-place plan on the input strides for a transform with transposed output.  Plans with such a step run in
+           one chunk (the step covers the whole batch). */
+        fa_transp t;
+        if (match_user_loops(rank, dims, hrank, hdims, mul_i, mul_o, 2, &t)) {
+            if (ri != ro) { if (rank == 0) p->tr_kind = FA_TR_COPY; }
+            else if (fa_transp_inplace_ok(&t) && inplace_same_locations(p))
+                p->tr_kind = (rank == 0) ? FA_TR_INPLACE : (inplace_ok_c2c(p) ? FA_TR_NONE : FA_TR_AFTER);
+            if (p->tr_kind) { p->tr = t; p->single_chunk = 1; }
+        }
+    }
     if (type == FA_C2C && ri == ro && !inplace_ok_c2c(p)) {
         /* strides differ: legal when both sides address the same locations; the whole problem then goes through a
-           dense scratch image (every read before every write), in one chunk */
+           dense scratch image (every read before every write), in one chunk -- unless the in-place step applies */
         if (ii != io || !inplace_same_locations(p)) { fa_plan_free(p); return NULL; }
-        p->via_scratch = 1;
+        p->via_scratch = !p->tr_kind;
         p->single_chunk = 1;
     }
     if (type != FA_C2C && (void *)ri == (void *)ro) {
@@ -655,6 +686,25 @@ static plan *mk_r2r(int rank, const fftw_iodim64 *dims, int hrank, const fftw_io
     /* in place with different layouts: one chunk, so that the first axis has read
        everything into scratch before anything is written back */
     if (in == out && !same) p->single_chunk = 1;
+    if (rank == 0) {
+        /* Rank 0 = a copy.  Two arrays: one tiled transposition when the loops form one.  One array: both sides must
+           address the same locations (the reference's rule for every in-place rdft problem, fftw_mkproblem_rdft,
+           fftw/fftw_api.c:9096, fftw_tensor_inplace_locations :17298); a square transposition runs in place, any other
+           problem that moves data goes through a dense scratch image in one chunk -- a single element-wise copy of an
+           array onto itself in a permuted order is a data race between workgroups. */
+        fa_transp t;
+        const int tr = match_user_loops(0, NULL, hrank, hdims, 1, 1, 1, &t);
+        if (in != out) {
+            if (tr) p->tr_kind = FA_TR_COPY;
+        } else {
+            /* as for c2c: the rule is asked only when the strides of the two sides differ */
+            if (!same && !inplace_same_locations(p)) { fa_plan_free(p); return NULL; }
+            if (tr && fa_transp_inplace_ok(&t)) p->tr_kind = FA_TR_INPLACE;
+            else if (tr || !same) p->via_scratch = 1;
+        }
+        if (p->tr_kind) p->tr = t;
+        if (p->tr_kind || p->via_scratch) p->single_chunk = 1;
+    }
     return finish(p, in, in, out, out);
 }
 

@@ -87,6 +87,25 @@ typedef struct {
     int dense;                  /* the axis interleaved with a 2-element loop is contiguous memory */
 } fa_axis;
 
+/* loops seen as a batched transposition of n0 x n1 matrices of tuples of vl contiguous doubles:
+       dst[c ldd + r vl + t] = src[r lds + c vl + t],   r < n0, c < n1, t < vl,
+   inside the outer loops b[0 .. nb) */
+typedef struct {
+    i64 n0, n1, lds, ldd, vl;
+    int nb;
+    fa_dim b[FA_MAXLOOPS];
+} fa_transp;
+
+/* plan.tr_kind: how the problem uses the transposition kernels (api.c decides on the caller's own loops, extent-1
+   ones included) */
+enum {
+    FA_TR_NONE = 0,
+    FA_TR_COPY,         /* rank 0, two arrays: the whole plan is one tiled transposition */
+    FA_TR_INPLACE,      /* rank 0, one array, square: the whole plan is one in-place step, no scratch */
+    FA_TR_AFTER         /* in-place transform whose output strides are the transposed input strides (square): the
+                           ordinary in-place plan on the input strides, then the in-place step */
+};
+
 struct fftw_plan_s {
     int type;                   /* FA_C2C / FA_R2C / FA_C2R / FA_R2R */
     int kinds[FA_MAXRANK];      /* FA_R2R: fftw_r2r_kind of every dim */
@@ -117,8 +136,10 @@ struct fftw_plan_s {
     i64 out_written;            /* number of doubles the plan writes in the output */
     int inplace;
     int single_chunk;           /* run the whole batch as one chunk */
-    int via_scratch;            /* in-place c2c problem whose input and output strides differ (same locations): the
-                                   result is built in a dense scratch image and copied to the output layout */
+    int via_scratch;            /* in-place c2c or rank-0 r2r problem whose input and output strides differ (same
+                                   locations): the result is built in a dense scratch image and copied to the output layout */
+    int tr_kind;                /* FA_TR_* */
+    fa_transp tr;
 
     void *stream;
     int dev_ready;
@@ -170,6 +191,14 @@ int  fa_device_init(struct fftw_plan_s *p);
 void fa_run(struct fftw_plan_s *p, double *ri, double *ii, double *ro, double *io);
 char *fa_sprint(const struct fftw_plan_s *p);
 fa_cfg fa_default_cfg(void);
+/* 1 and *t when the loops l[0 .. nl) (strides in doubles, `unit` doubles per element) are a transposition the tile
+   kernels take: positive strides, an optional inner tuple loop of unit stride on both sides, one loop of tuple stride
+   on the output and another of tuple stride on the input (extent-1 loops count when their strides fit), the rest
+   outer batch loops that step over a whole matrix on both sides */
+int fa_match_transpose(const fa_dim *l, int nl, i64 unit, fa_transp *t);
+/* 1 when *t is square with equal leading dimensions, every batch loop has the same stride on both sides and the
+   matrices of the batch do not overlap: the in-place step applies */
+int fa_transp_inplace_ok(const fa_transp *t);
 
 /* api.c */
 struct fftw_plan_s *fa_unaligned_twin(const struct fftw_plan_s *p);

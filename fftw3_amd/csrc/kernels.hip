@@ -1523,6 +1523,14 @@ static int launch_step_kind(const fftw_amd_step_desc *d, double *const *bufs,
     case FFTW_AMD_STEP_HERM_EXPAND: {
         CopyArgs ca;
         dim3 grid;
+        if (d->kind == FFTW_AMD_STEP_COPY && d->variant == FFTW_AMD_K_TRANSPOSE) {
+            /* no other executor: a transposition step the tile kernels cannot take is an internal error */
+            if (fa_launch_transpose(d, bufs, cs, cn, st)) {
+                fprintf(stderr, "fftw3_amd: internal error: transposition step in an unsupported layout\n");
+                return -1;
+            }
+            return 0;
+        }
         if (!fill_copy_args(&ca, d, bufs, tables, cs, cn, &grid)) return 0;
         if (d->kind == FFTW_AMD_STEP_COPY) {
             if (d->flags & (FFTW_AMD_F_PERM_SRC | FFTW_AMD_F_PERM_DST)) {

@@ -133,6 +133,9 @@ int fa_launch_r2crows1(const fftw_amd_step_desc *d, double *const *bufs, void *c
 /* kernels_sq.hip: FFTW_AMD_F_LO_DFT steps (rows + a DFT across the rows of a tile) */
 int fa_launch_lo_dft(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
 
+/* kernels_tr.hip: transposition steps (FFTW_AMD_STEP_COPY of variant FFTW_AMD_K_TRANSPOSE) */
+int fa_launch_transpose(const fftw_amd_step_desc *d, double *const *bufs, i64 cs, i64 cn, hipStream_t st);
+
 /* kernels_rr1.hip, kernels_rr2.hip: the upper two thirds of rr_menu.inc (rr_dispatch.hpp) */
 int fa_dispatch_rr_part1(int L, const P1024Args &pa, dim3 grid, hipStream_t st, bool in_t, bool out_t, int tw);
 int fa_dispatch_rr_part2(int L, const P1024Args &pa, dim3 grid, hipStream_t st, bool in_t, bool out_t, int tw);

@@ -505,6 +505,105 @@ static void emit_copy(plan *p, int kind, fa_loc src, fa_loc dst, i64 K, i64 Kval
     step_set_dims(p, s, dims, nd, -1);
 }
 
+/* ------------------------------------------------------- transpositions */
+
+/* FFTW_AMD_NO_TRANSPOSE=1 keeps every copy on the element-wise kernels (measurements: tools/perf/perf_transpose.py) */
+static int transposes_enabled(void) {
+    static int on = -1;
+    if (on < 0) { const char *e = getenv("FFTW_AMD_NO_TRANSPOSE"); on = !(e && atoi(e)); }
+    return on;
+}
+
+int fa_match_transpose(const fa_dim *l, int nl, i64 unit, fa_transp *t) {
+    int ti, i, a, b;
+    if (!transposes_enabled()) return 0;
+    for (i = 0; i < nl; ++i) if (l[i].n < 1 || (l[i].n > 1 && (l[i].is <= 0 || l[i].os <= 0))) return 0;
+    /* with an inner tuple loop first (a loop of unit stride on both sides, at most 8 doubles), then without */
+    for (ti = 0; ti <= nl; ++ti) {
+        const int tl = ti < nl ? ti : -1;
+        i64 vl = unit;
+        int best = -1, ba = -1, bb = -1;
+        if (tl >= 0) {
+            if (l[tl].n < 2 || l[tl].is != unit || l[tl].os != unit || l[tl].n * unit > 8) continue;
+            vl = l[tl].n * unit;
+        }
+        for (a = 0; a < nl; ++a)
+            for (b = 0; b < nl; ++b) {
+                int score;
+                if (a == b || a == tl || b == tl) continue;
+                if (l[a].os != vl || l[b].is != vl) continue;
+                if (l[a].is < l[b].n * vl || l[b].os < l[a].n * vl) continue;
+                score = (l[a].n > 1) + (l[b].n > 1);
+                if (score > best) { best = score; ba = a; bb = b; }
+            }
+        if (best < 0) continue;
+        t->n0 = l[ba].n; t->lds = l[ba].is;
+        t->n1 = l[bb].n; t->ldd = l[bb].os;
+        t->vl = vl;
+        t->nb = 0;
+        for (i = 0; i < nl; ++i) {
+            if (i == ba || i == bb || i == tl || l[i].n == 1) continue;
+            if (t->nb >= FFTW_AMD_MAX_DIMS - 2 || t->nb >= FA_MAXLOOPS) return 0;
+            /* a batch loop is an OUTER loop: it steps over a whole matrix on both sides (a third loop interleaved
+               with the matrix is a permutation of three loops, which stays on the element-wise kernels) */
+            if (l[i].is < (t->n0 - 1) * t->lds + t->n1 * vl || l[i].os < (t->n1 - 1) * t->ldd + t->n0 * vl) return 0;
+            t->b[t->nb++] = l[i];
+        }
+        return 1;
+    }
+    return 0;
+}
+
+int fa_transp_inplace_ok(const fa_transp *t) {
+    i64 n[FA_MAXLOOPS + 2], st[FA_MAXLOOPS + 2];
+    int i, j, k = 0;
+    if (t->n0 != t->n1 || t->lds != t->ldd) return 0;
+    n[k] = t->n1; st[k++] = t->vl;
+    n[k] = t->n0; st[k++] = t->lds;
+    for (i = 0; i < t->nb; ++i) {
+        if (t->b[i].is != t->b[i].os) return 0;
+        n[k] = t->b[i].n; st[k++] = t->b[i].is;
+    }
+    for (i = 1; i < k; ++i)                       /* by stride; every loop must step over the whole of the previous one */
+        for (j = i; j > 0 && st[j] < st[j - 1]; --j) {
+            i64 x = st[j]; st[j] = st[j - 1]; st[j - 1] = x;
+            x = n[j]; n[j] = n[j - 1]; n[j - 1] = x;
+        }
+    for (i = 1; i < k; ++i) if (n[i] > 1 && st[i] < n[i - 1] * st[i - 1]) return 0;
+    return 1;
+}
+
+/* One transposition step (kernels_tr.hip).  The fields mean what they mean for every copy: the tuple is the copy's
+   own index (aux_n elements), the two matrix loops and the batch loops are its dims.  All extents are the whole
+   problem's: plans that hold such a step run in one chunk. */
+static void emit_transpose(plan *p, fa_loc src, fa_loc dst, const fa_transp *t, i64 unit, int inplace) {
+    fftw_amd_step_desc *s = new_step(p, FFTW_AMD_STEP_COPY);
+    int i;
+    s->src_buf = src.buf; s->src_base = src.base; s->src_im = unit == 2 ? 1 : 0;
+    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = unit == 2 ? 1 : 0;
+    s->flags = (unit == 1 ? (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT) : 0) | (inplace ? FFTW_AMD_F_PAIR_SWAP : 0);
+    s->is_l = s->os_l = unit;
+    s->aux_n = s->aux_valid = t->vl / unit;
+    s->variant = FFTW_AMD_K_TRANSPOSE;
+    s->tile = t->vl == unit ? 32 : 16;
+    s->dim_n[0] = t->n0; s->dim_is[0] = t->lds; s->dim_os[0] = t->vl;
+    s->dim_n[1] = t->n1; s->dim_is[1] = t->vl;  s->dim_os[1] = t->ldd;
+    for (i = 0; i < t->nb; ++i) {
+        s->dim_n[2 + i] = t->b[i].n; s->dim_is[2 + i] = t->b[i].is; s->dim_os[2 + i] = t->b[i].os;
+    }
+    s->ndims = 2 + t->nb;
+}
+
+/* interleaved complex data the 16-byte kernels of a c2c problem can take: the planner's arrays aligned.  (The
+   launcher itself takes any alignment: a new-array execution may still pass an offset array.) */
+static int transp_layout_ok(const plan *p, fa_loc src, fa_loc dst) {
+    if (p->type == FA_R2R) return 1;
+    if (p->type != FA_C2C || src.im != 1 || dst.im != 1 || (src.base % 2) || (dst.base % 2)) return 0;
+    if ((src.buf == 0 || dst.buf == 0) && ((size_t)p->ri % 16)) return 0;
+    if ((src.buf == 1 || dst.buf == 1) && ((size_t)p->ro % 16)) return 0;
+    return 1;
+}
+
 /* ------------------------------------------------------------- one axis */
 
 static void fa_emit_axis(plan *p, const fa_axis *ax);
@@ -1268,8 +1367,69 @@ static int emit_rows_lo_dft(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_ou
 
 static void build_c2c_on(plan *p, fa_loc in, fa_loc out);
 
+/* One copy src -> dst over ALL dims of the problem as loops (transform dims, then the howmany dims of the current
+   chunk; strides as p->dims / p->hdims hold them now): a tiled transposition when the loops form one
+   (fa_match_transpose), else the element-wise copy -- complex: a pass of length 1 on the LDS kernel, real:
+   copy_kernel (reference rank0 solvers, fftw/fftw_api.c:9655-9720). */
+static void emit_loops_copy(plan *p, fa_loc src, fa_loc dst, int contig_k) {
+    const i64 unit = p->type == FA_R2R ? 1 : 2;
+    fa_dim l[2 * FA_MAXRANK];
+    fa_transp t;
+    fa_axis ax;
+    sdim d[FA_MAXLOOPS];
+    int i, nl = 0, nd;
+    for (i = 0; i < p->rank; ++i) l[nl++] = p->dims[i];
+    for (i = 0; i < p->hrank; ++i) { l[nl] = p->hdims[i]; if (i == 0) l[nl].n = p->chunk; ++nl; }
+    if (transp_layout_ok(p, src, dst) && fa_match_transpose(l, nl, unit, &t)) {
+        emit_transpose(p, src, dst, &t, unit, 0);
+        return;
+    }
+    memset(&ax, 0, sizeof(ax));
+    if (collect_loops(p, p->dims, p->rank, -1, NULL, 0, &ax)) { p->failed = 1; return; }
+    nd = loops_to_sdims(&ax, d, 0);
+    if (unit == 2) { emit_pass(p, src, dst, 1, 0, 0, d, nd, 0, 0); return; }
+    if (contig_k) {
+        /* a loop that is contiguous on both sides becomes the copy's own index: copy_kernel then gives a workgroup 256
+           neighbouring elements instead of one (the plain half of an in-place plan: 16 GB/s otherwise) */
+        for (i = 0; i < nd; ++i)
+            if (!d[i].is_batch && d[i].is == 1 && d[i].os == 1 && d[i].n > 1 && d[i].n < 0x7fffffffLL) {
+                const i64 K = d[i].n;
+                d[i].n = 1;                      /* step_set_dims drops it */
+                emit_copy(p, FFTW_AMD_STEP_COPY, src, dst, K, K, 1, 1, d, nd, FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT, -1, -1);
+                return;
+            }
+    }
+    emit_copy(p, FFTW_AMD_STEP_COPY, src, dst, 1, 1, 0, 0, d, nd, FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT, -1, -1);
+}
+
+/* the whole of a rank-0 problem (c2c and r2r) */
+static void build_rank0(plan *p, fa_loc in, fa_loc out) {
+    const i64 unit = p->type == FA_R2R ? 1 : 2;
+    if (p->tr_kind == FA_TR_COPY || p->tr_kind == FA_TR_INPLACE) {
+        emit_transpose(p, in, out, &p->tr, unit, p->tr_kind == FA_TR_INPLACE);
+        return;
+    }
+    emit_loops_copy(p, in, out, 0);
+}
+
 static void build_c2c(plan *p) {
     fa_loc in = { 0, 0, p->in_im }, out = { 1, 0, p->out_im };
+    if (p->tr_kind == FA_TR_AFTER) {
+        /* Output strides = the transposed input strides, square (the reference's dft-ct-dif + q1 case, A.c:2204-2250,
+           2596-2727): the ordinary in-place problem on the INPUT strides, in one chunk, then the in-place square
+           transposition -- no more scratch than that in-place plan needs. */
+        fa_dim sd[FA_MAXRANK], sh[FA_MAXRANK];
+        int i;
+        memcpy(sd, p->dims, sizeof(sd));
+        memcpy(sh, p->hdims, sizeof(sh));
+        for (i = 0; i < p->rank; ++i) p->dims[i].os = p->dims[i].is;
+        for (i = 0; i < p->hrank; ++i) p->hdims[i].os = p->hdims[i].is;
+        build_c2c_on(p, in, out);
+        memcpy(p->dims, sd, sizeof(sd));
+        memcpy(p->hdims, sh, sizeof(sh));
+        if (!p->failed) emit_transpose(p, out, out, &p->tr, 2, 1);
+        return;
+    }
     if (p->via_scratch) {
         /* in-place with different strides on the two sides (same locations): transform into a dense row-major
            scratch image [hdims...][dims...], then copy it to the output layout -- every read of the user's array
@@ -1277,10 +1437,8 @@ static void build_c2c(plan *p) {
            DIF + transpose codelets or with buffers (A.c:2204-2250, 2596-2727); see api.c inplace_same_locations. */
         fa_dim sd[FA_MAXRANK], sh[FA_MAXRANK];
         fa_loc scr;
-        fa_axis ax;
-        sdim d[FA_MAXLOOPS];
         i64 stride = 2, total;
-        int i, nd, sbuf;
+        int i, sbuf;
         memcpy(sd, p->dims, sizeof(sd));
         memcpy(sh, p->hdims, sizeof(sh));
         for (i = p->rank - 1; i >= 0; --i) { p->dims[i].os = stride; stride *= p->dims[i].n; }
@@ -1293,15 +1451,11 @@ static void build_c2c(plan *p) {
         scr.buf = sbuf; scr.base = 0; scr.im = 1;
         build_c2c_on(p, in, scr);
         /* the copy: all dims as loops, source = dense strides, destination = the user's output strides */
-        memset(&ax, 0, sizeof(ax));
         for (i = 0; i < p->rank; ++i) p->dims[i].is = p->dims[i].os;
         for (i = 0; i < p->hrank; ++i) p->hdims[i].is = p->hdims[i].os;
         for (i = 0; i < p->rank; ++i) p->dims[i].os = sd[i].os;
         for (i = 0; i < p->hrank; ++i) p->hdims[i].os = sh[i].os;
-        if (!p->failed && collect_loops(p, p->dims, p->rank, -1, NULL, 0, &ax) == 0) {
-            nd = loops_to_sdims(&ax, d, 0);
-            emit_pass(p, scr, out, 1, 0, 0, d, nd, 0, 0);
-        } else p->failed = 1;
+        if (!p->failed) emit_loops_copy(p, scr, out, 0);
         memcpy(p->dims, sd, sizeof(sd));
         memcpy(p->hdims, sh, sizeof(sh));
         buf_release(p, sbuf);
@@ -1316,13 +1470,7 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
     int sw_out = (p->sign > 0) ? FFTW_AMD_F_SWAP_OUT : 0;
     if (p->rank == 0) {
         /* rank-0 "transform" = strided copy (reference rank0 solvers) */
-        fa_axis ax;
-        sdim d[FA_MAXLOOPS];
-        int nd;
-        memset(&ax, 0, sizeof(ax));
-        if (collect_loops(p, p->dims, 0, -1, NULL, 0, &ax)) { p->failed = 1; return; }
-        nd = loops_to_sdims(&ax, d, 0);
-        emit_pass(p, in, out, 1, 0, 0, d, nd, 0, 0);
+        build_rank0(p, in, out);
         return;
     }
     if (emit_rows_lo_dft(p, in, out, sw_in, sw_out)) return;
@@ -2221,16 +2369,31 @@ static void emit_r2r_axis(plan *p, int kind, i64 n, const fa_axis *axp, fa_loc i
 static void build_r2r(plan *p) {
     int a, first = 1;
     fa_loc in = { 0, 0, 0 }, out = { 1, 0, 0 };
+    if (p->rank == 0 && p->via_scratch) {
+        /* in place with different strides on the two sides (same locations, no square transposition): through a dense
+           row-major scratch image in one chunk, as build_c2c does -- every read of the array precedes every write.
+           One half is a plain contiguous copy, the other the transposition. */
+        fa_dim sh[FA_MAXRANK];
+        fa_loc scr;
+        i64 stride = 1;
+        int i, sbuf;
+        memcpy(sh, p->hdims, sizeof(sh));
+        for (i = p->hrank - 1; i >= 0; --i) {
+            p->hdims[i].os = stride;
+            stride *= (i == 0 ? p->chunk : p->hdims[i].n);
+        }
+        sbuf = buf_acquire(p, stride);
+        scr.buf = sbuf; scr.base = 0; scr.im = 0;
+        emit_loops_copy(p, in, scr, 1);
+        for (i = 0; i < p->hrank; ++i) { p->hdims[i].is = p->hdims[i].os; p->hdims[i].os = sh[i].os; }
+        if (!p->failed) emit_loops_copy(p, scr, out, 1);
+        memcpy(p->hdims, sh, sizeof(sh));
+        buf_release(p, sbuf);
+        return;
+    }
     if (p->rank == 0) {
         /* rank 0: strided copy of reals (reference rdft rank0 solver, fftw/fftw_api.c:9655-9720) */
-        fa_axis ax;
-        sdim d[FA_MAXLOOPS];
-        int nd;
-        memset(&ax, 0, sizeof(ax));
-        if (collect_loops(p, p->dims, 0, -1, NULL, 0, &ax)) { p->failed = 1; return; }
-        nd = loops_to_sdims(&ax, d, 0);
-        emit_copy(p, FFTW_AMD_STEP_COPY, in, out, 1, 1, 0, 0, d, nd,
-                  FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT, -1, -1);
+        build_rank0(p, in, out);
         return;
     }
     for (a = p->rank - 1; a >= 0; --a) {
@@ -2822,7 +2985,10 @@ char *fa_sprint(const plan *p) {
     sapp(s, cap, &len, "(hip-%s batch=%lld chunk=%lld", tn, p->batch, p->chunk);
     for (i = 0; i < p->nsteps; ++i) {
         const fftw_amd_step_desc *d = &p->steps[i];
-        sapp(s, cap, &len, "\n  (%s", kind_name(d->kind));
+        if (d->kind == FFTW_AMD_STEP_COPY && d->variant == FFTW_AMD_K_TRANSPOSE)
+            sapp(s, cap, &len, "\n  (%s", (d->flags & FFTW_AMD_F_PAIR_SWAP) ? "transpose-inplace" : "transpose");
+        else
+            sapp(s, cap, &len, "\n  (%s", kind_name(d->kind));
         if (d->kind == FFTW_AMD_STEP_PASS) {
             /* which kernel runs the pass: reg32x32 / reg2 / reg3 = register-resident
                (pass1024 / passrr / pass3s), lds = runtime-radix LDS kernel + its radices */

@@ -330,8 +330,13 @@ enum {
     FFTW_AMD_K_R2C = 4,         /* fused real rows -> half spectra (r2crows.hpp), with FFTW_AMD_F_R2C_ROWS */
     FFTW_AMD_K_C2R = 5,         /* fused half spectra -> real rows, with FFTW_AMD_F_C2R_ROWS */
     FFTW_AMD_K_R1 = 6,          /* one-stage register kernel: dense rows of 2 ... 32 points, one butterfly per row */
-    FFTW_AMD_K_BLUE = 7         /* Bluestein's algorithm for a whole row in one kernel (pass3b.hpp): L = padded length nb,
+    FFTW_AMD_K_BLUE = 7,        /* Bluestein's algorithm for a whole row in one kernel (pass3b.hpp): L = padded length nb,
                                    aux_n = n, tw_lo / tw_hi = ids of the chirp and the kernel table */
+    FFTW_AMD_K_TRANSPOSE = 8    /* FFTW_AMD_STEP_COPY that is a batched transposition of n0 x n1 matrices of tuples, through
+                                   LDS tiles (transpose.hpp): dims[0] = (n0, source leading dimension, vl), dims[1] =
+                                   (n1, vl, destination leading dimension), dims[2 ...] the outer batch loops, the tuple of
+                                   vl doubles as the copy's own index (aux_n elements at is_l = os_l).  Every field keeps
+                                   the meaning it has for any other copy */
 };
 
 enum {
@@ -354,7 +359,7 @@ enum {
     FFTW_AMD_F_LO_DFT    = 1 << 14,/* pass: the inner tile component is transformed too -- a DFT of length tile_lo_n across the
                                       tile's tile_lo_n sequences (no twiddle), i.e. the step is the 2-D DFT tile_lo_n x L of every
                                       tile (pass3q.hpp: four rows of 4096 points, the last trip of a 4096 x 4096 transform) */
-    FFTW_AMD_F_REAL_DEC  = 1 << 15 /* pass: the last trip of a two-trip r2c transform of n = L1 x L real points (pass3t_kernel,
+    FFTW_AMD_F_REAL_DEC  = 1 << 15,/* pass: the last trip of a two-trip r2c transform of n = L1 x L real points (pass3t_kernel,
                                       RD = 1).  The tile dim runs over the rows k1 = 0 ... L1 / 2 (dim_n[0] = L1 / 2 + 1) of the
                                       scratch image Z[k1][c] (rows at dim_is[0], pairs at is_l) left by the complex pass of
                                       length L1 over the real input read as pairs; row k1 is loaded as
@@ -363,6 +368,10 @@ enum {
                                       k1 dim_os[0] + k2 os_l, the others conjugated to (L1-k1) dim_os[0] + (L-1-k2) os_l
                                       (not for k1 = 0 and L1 / 2, whose second halves repeat their first; X[n / 2] comes from
                                       row 0).  No fallback executor: planned only for aligned interleaved arrays */
+    FFTW_AMD_F_PAIR_SWAP = 1 << 16 /* transposition step (FFTW_AMD_K_TRANSPOSE) of a square matrix onto itself (source and
+                                      destination are the same array, equal leading dimensions): workgroups exchange the tile
+                                      pairs (ti, tj) / (tj, ti) in place, no scratch.  As for every copy, all reads happen
+                                      before any write of the same word */
 };
 
 int fftw_amd_plan_num_steps(const fftw_plan p);
