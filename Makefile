@@ -65,7 +65,15 @@ $(LIBDIR)/libfftw3_amd.so: $(OBJS)
 oracle:
 	$(MAKE) -C oracle
 
-clean:
-	rm -f $(OBJS) $(LIBDIR)/*.so*
+# host-only sanitizer check of the two-trip c2r planner path: the C sources under ASan + UBSan, the HIP units (host-side
+# tables only) from the ordinary library.  Planning needs no device.
+SANSRC := $(CSRC)/api.c $(CSRC)/planner.c $(CSRC)/sharded.c $(CSRC)/slab.c $(CSRC)/slab1d.c $(CSRC)/hostmath.c
+san-c2r: $(LIBDIR)/libfftw3_amd.so
+	mkdir -p build
+	$(CC) -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -I$(CSRC) tools/san/plan_c2r_decimated.c $(SANSRC) -o build/plan_c2r_decimated_san -L$(LIBDIR) -lfftw3_amd -Wl,-rpath,$(abspath $(LIBDIR)) -lm -lpthread -ldl
+	./build/plan_c2r_decimated_san
 
-.PHONY: all oracle clean
+clean:
+	rm -f $(OBJS) $(LIBDIR)/*.so* build/plan_c2r_decimated_san
+
+.PHONY: all oracle clean san-c2r

@@ -58,6 +58,7 @@ F_R2C_ROWS = 1024
 F_C2R_ROWS = 2048
 F_LO_DFT = 1 << 14
 F_REAL_DEC = 1 << 15
+F_REAL_DEC_C2R = 1 << 17
 F_PAIR_SWAP = 1 << 16
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
 K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE = range(9)

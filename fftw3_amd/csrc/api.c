@@ -188,8 +188,9 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
             fa_cfg best = p->cfg, c;
             double best_ms = -1.0;
             int ci, pi, li, st, lf, rd, nl = (p->flags & (FFTW_PATIENT | FFTW_EXHAUSTIVE)) ? 2 : 1;
-            /* r2c problems: also the plan decimated over the real data (cfg.real_dec), with the default chunking only */
-            const int nrd = (p->type == FA_R2C) ? 2 : 1;
+            /* r2c and c2r problems: also the two-trip plan decimated over the real data (cfg.real_dec), with the default
+               chunking only */
+            const int nrd = (p->type == FA_R2C || p->type == FA_C2R) ? 2 : 1;
             for (rd = 0; rd < nrd; ++rd)
             for (ci = 0; ci < 5; ++ci)
                 for (pi = 0; pi < 2; ++pi)

@@ -1350,6 +1350,12 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
         fprintf(stderr, "fftw3_amd: internal error: real-decimated rows step with an unsupported layout\n");
         abort();
     }
+    if (d->flags & FFTW_AMD_F_REAL_DEC_C2R) {
+        /* the first trip of a two-trip c2r: likewise one executor, no fallback */
+        if (fa_launch_pass3tw(d, bufs, tables, cs, cn, st) == 0) return 0;
+        fprintf(stderr, "fftw3_amd: internal error: c2r-decimated rows step with an unsupported layout\n");
+        abort();
+    }
     if (d->variant == FFTW_AMD_K_P1024 && launch_p1024(d, bufs, tables, cs, cn, st) == 0) return 0;
     if (d->variant == FFTW_AMD_K_BLUE) return fa_launch_blue(d, bufs, tables, cs, cn, st);
     if (d->variant == FFTW_AMD_K_R1 && fa_launch_pass1r(d, bufs, tables, cs, cn, st) == 0) return 0;

@@ -3,7 +3,8 @@
  * per workgroup for the lengths of r3tw_menu.inc (1080 ... 2048): tiles of 16384 elements hold 8 ... 15 sequences,
  * i.e. 128 ... 240-byte segments on the strided side, where the 256-item tiles of kernels_r3.hip hold 4 ... 7
  * (64 ... 112 bytes, about 3.2 TB/s).  Serves a strided axis of such a length in one trip (2-D / 3-D transforms)
- * and the 2048-point first pass of the two-trip 2^21 plan.  One workgroup per CU.
+ * and the 2048-point first pass of the two-trip 2^21 plan; the 2048-point rows trips of the two-trip real plans (r2c: RD = 1,
+ * c2r: RD = 2).  One workgroup per CU.
  */
 #include "common.hpp"
 #include "pass1024.hpp"
@@ -37,6 +38,8 @@ static int dispatch_3tw(const P1024Args &pa, dim3 grid, hipStream_t st, bool in_
 
 /* 1 = the length has the real-decimated rows form (FFTW_AMD_F_REAL_DEC: last trip of a two-trip r2c) */
 extern "C" int fa_hip_r3tw_rdec(int L) { return L == 2048; }
+/* 1 = the length has the c2r-decimated rows form (FFTW_AMD_F_REAL_DEC_C2R: first trip of a two-trip c2r) */
+extern "C" int fa_hip_r3tw_cdec(int L) { return L == 2048; }
 
 /* sequences per tile of the 512-item strided kernel for length L (0: none) */
 extern "C" int fa_hip_r3tw_tile(int L) {
@@ -53,11 +56,18 @@ int fa_launch_pass3tw(const fftw_amd_step_desc *d, double *const *bufs, void *co
     P1024Args pa;
     const int T = fa_hip_r3tw_tile(d->L);
     const bool rdec = (d->flags & FFTW_AMD_F_REAL_DEC) != 0;
+    const bool cdec = (d->flags & FFTW_AMD_F_REAL_DEC_C2R) != 0;
+    const int swaps = FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_SWAP_OUT;
     if (T <= 0 || d->tile != T || d->src_im != 1 || d->dst_im != 1 || d->tile_lo_n > 1 ||
         (d->flags & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT | FFTW_AMD_F_CONJ_OUT | FFTW_AMD_F_LO_DFT)))
         return 1;
     if (rdec && (!fa_hip_r3tw_rdec(d->L) || (d->flags & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_SWAP_OUT)) || !(d->flags & FFTW_AMD_F_TW_IN) ||
                  d->tw_n == 0 || d->dim_tw[0] != 1 || d->dim_n[0] < 2 || d->batch_dim == 0))
+        return 1;
+    /* the c2r twin is a backward step: it carries BOTH swap flags (the kernel form exchanges re and im itself, while
+       loading and in its pair exchange), the twiddle on the output, and never the forward form's flag */
+    if (cdec && (rdec || !fa_hip_r3tw_cdec(d->L) || (d->flags & swaps) != swaps || (d->flags & FFTW_AMD_F_TW_IN) ||
+                 d->tw_n == 0 || d->dim_tw[0] != 1 || d->dim_n[0] < 2 || d->batch_dim == 0 || d->is_l != (d->dim_n[0] - 1) * 2 * d->dim_is[0]))
         return 1;
     const StepGeom g = fa_step_geom(d, bufs, cs, cn);
     if (!g.aligned() || !g.even_l() || !g.even_dims()) return 1;
@@ -82,6 +92,12 @@ int fa_launch_pass3tw(const fftw_amd_step_desc *d, double *const *bufs, void *co
     if (rdec) {
         if (in_t || !out_t || d->L != 2048) return 1;
         launch_3tw_variant<8, 16, 16, false, 2, 1>(pa, grid, st);
+        return 0;
+    }
+    if (cdec) {
+        if (!in_t || out_t || d->L != 2048) return 1;
+        pa.flags &= ~swaps;                       /* applied by the form itself */
+        launch_3tw_variant<8, 16, 16, true, 1, 2>(pa, grid, st);
         return 0;
     }
     int tw = d->tw_n == 0 ? 0 : ((d->flags & FFTW_AMD_F_TW_IN) ? 2 : 1);

@@ -345,6 +345,26 @@ template <int R1, int R2, int R3, int NT = 256> struct P3TGeom {
    conjugate of the others at n - (k1 + L1 k2) = (L1 - k1) + L1 (L - 1 - k2) -- the half spectrum 0 ... n / 2, every
    store a run of T consecutive outputs.  Reference counterpart: the rdft2 Cooley-Tukey node over real codelets,
    hc2cf / r2cf (fftw/rdft_scalar/r2cf/hc2cfdft_*.c under ct_hc2c_direct_apply, fftw/fftw_api.c:5831). */
+/* RD = 2 (column load form with the twiddle on the output, FFTW_AMD_F_REAL_DEC_C2R): the FIRST trip of the two-trip
+   c2r transform, the plan above run backward.  The tile dim runs over the rows k1 = 0 ... L1 / 2 of the half spectrum
+   read as [L][L1] (k1 contiguous: the column load geometry); the row is Y[k2] = X[k1 + L1 k2] for k2 < L / 2 and
+   conj X[(L1 - k1) + L1 (L - 1 - k2)] above -- the mirror is an address and a sign on the LOAD side, and the butterfly
+   input i = k2 / M decides at compile time which half an element is in.  The transform is backward by the swap
+   identity (re and im exchanged while loading and again below), so the stages are the forward ones and the output
+   twiddle conj w_n^(k1 j2) of HAS_TW = 1 becomes w_n^(+k1 j2).  After stage C an item holds B = swap A[k1][j2] for
+   j2 = kb + R1 R2 c; the two members of a pair (j2 even, j2 odd) sit in the lanes tid and tid ^ T of one wave
+   (cd1 = (tid / T) % R1, R1 even), and a row rotation by T = 8 lanes (DPP) hands each the other's value:
+        Z[k1][c]      = A[k1][2c] + i A[k1][2c+1]            stored by the even lane
+        Z[L1 - k1][c] = conj A[k1][2c] + i conj A[k1][2c+1]  stored by the odd lane
+   -- R3 stores per item as in every other form.  The rows k1 = 0 and L1 / 2 are their own mirrors: the even lane
+   stores the real parts, the odd lane nothing.  Reference counterpart: hc2cbdft_*.c under ct_hc2c_direct_apply
+   (fftw/fftw_api.c:5551-5603). */
+template <int CTRL> FA_DEV double fa_dpp_f64(double v) {
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
 /* FA_P3T_TIMELINE (tests/micro/p3t_timeline.hip only, never in the product): wave 0 of every workgroup leaves
    wall-clock stamps at the phase boundaries in a.dbg[16 * blockIdx.x + k] */
 #ifdef FA_P3T_TIMELINE
@@ -355,7 +375,9 @@ template <int R1, int R2, int R3, int NT = 256> struct P3TGeom {
 template <int R1, int R2, int R3, bool IN_T, int HAS_TW, int NT = 256, int RD = 0>
 __global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
 pass3t_kernel(const P1024Args a) {
-    static_assert(RD == 0 || (!IN_T && HAS_TW == 2 && (R2 * R3) % 2 == 0 && R3 % 2 == 0), "real-decimated rows: rows form, twiddle on the input");
+    static_assert(RD == 0 || RD == 2 || (!IN_T && HAS_TW == 2 && (R2 * R3) % 2 == 0 && R3 % 2 == 0), "real-decimated rows: rows form, twiddle on the input");
+    static_assert(RD != 2 || (IN_T && HAS_TW == 1 && R1 % 2 == 0 && P3TGeom<R1, R2, R3, NT>::T == 8 && NT % (8 * R1) == 0),
+                  "c2r-decimated rows: column loads, twiddle on the output, pair partners 8 lanes apart");
     extern __shared__ __attribute__((aligned(16))) double plane[];
     typedef P3TGeom<R1, R2, R3, NT> G;
     constexpr int M = G::M, T = G::T, QA = G::QA, QB = G::QB, QC = G::QC;
@@ -427,6 +449,29 @@ pass3t_kernel(const P1024Args a) {
                 x[u][i] = odd ? c_make(0.5 * (v1.y + v2.y), 0.5 * (v2.x - v1.x))
                               : c_make(0.5 * (v1.x + v2.x), 0.5 * (v1.y - v2.y));
             }
+            continue;
+        }
+        if constexpr (RD == 2) {
+            /* element k2 = aa + M i of row k1, already swapped: (im, re) below L / 2, the conjugate's (-im, re) above */
+            const i64 k1 = t0 + t, L1 = 2 * (a.dn[0] - 1);
+            const double *lo = a.src + soff + k1 * a.dis[0] + (i64)aa[u] * a.is_l;
+            const double *hi = a.src + soff + (L1 - k1) * a.dis[0] + (i64)(G::L - 1 - aa[u]) * a.is_l;
+            const i64 step = (i64)M * a.is_l;
+            const bool real0 = k1 == 0 && aa[u] == 0;              /* X[0] and X[n / 2]: the imaginary part reads as 0 */
+            auto loads = [&](auto ntc) {
+                constexpr bool NTL = decltype(ntc)::value;
+#pragma unroll
+                for (int i = 0; i < R1 / 2; ++i) {
+                    const cplx v = ld_cplx<NTL>(lo + i * step);
+                    x[u][i] = c_make((i == 0 && real0) ? 0.0 : v.y, v.x);
+                }
+#pragma unroll
+                for (int i = R1 / 2; i < R1; ++i) {
+                    const cplx v = ld_cplx<NTL>(hi - i * step);
+                    x[u][i] = c_make((i == R1 / 2 && real0) ? 0.0 : -v.y, v.x);
+                }
+            };
+            if (a.flags & FFTW_AMD_F_NT_IN) loads(std::true_type{}); else loads(std::false_type{});
             continue;
         }
         const double *p = src + (i64)aa[u] * a.is_l + (i64)t * a.dis[0];
@@ -596,6 +641,33 @@ pass3t_kernel(const P1024Args a) {
                 }
             };
             if (a.flags & FFTW_AMD_F_NT_OUT) stores(std::true_type{}); else stores(std::false_type{});
+            continue;
+        }
+        if constexpr (RD == 2) {
+            /* pair c = (kb >> 1) + (R1 R2 / 2) c'.  With B = swap A mine and P = swap A of the partner lane the even
+               lane's Z[k1][c] is (B.y - P.x, B.x + P.y) and the odd lane's Z[L1 - k1][c] the same two numbers the
+               other way round; every lane takes part in the exchange, the one branch goes around the stores */
+            const i64 k1 = t0 + tc, L1 = 2 * (a.dn[0] - 1);
+            const bool edge = k1 == 0 || 2 * k1 == L1;          /* rows that are their own mirror */
+            const bool odd = (cd1[w] & 1) != 0;
+            double *pz = a.dst + doff + (odd ? L1 - k1 : k1) * a.dos[0] + (i64)(kb >> 1) * a.os_l;
+            const i64 pstep = (i64)(R1 * R2 / 2) * a.os_l;
+#pragma unroll
+            for (int c = 0; c < R3; ++c) {
+                const cplx b = z[w][RB<R3>::slot(c)];
+                const double px = fa_dpp_f64<0x128>(b.x), py = fa_dpp_f64<0x128>(b.y);      /* row_ror:8 = lane ^ 8 */
+                const double s = b.x + py, d = b.y - px;
+                z[w][RB<R3>::slot(c)] = odd ? c_make(s, d) : (edge ? c_make(b.y, py) : c_make(d, s));
+            }
+            if (!(odd && edge)) {
+                if (a.flags & FFTW_AMD_F_NT_OUT) {
+#pragma unroll
+                    for (int c = 0; c < R3; ++c) st_cplx<true>(pz + c * pstep, z[w][RB<R3>::slot(c)]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < R3; ++c) st_cplx<false>(pz + c * pstep, z[w][RB<R3>::slot(c)]);
+                }
+            }
             continue;
         }
         if constexpr (NT > 256) {

@@ -1919,11 +1919,100 @@ static void build_r2c(plan *p) {
    `cur` is the user's real r2r input of stride cs and the tangle step applies
    that prologue while loading (even lengths only, see r2r_can_fuse)
    ps / pim: pair geometry of the real output, as in emit_r2c_axis */
+/* The backward twin of emit_r2c_decimated: a long c2r transform in TWO trips, n = L1 x L2 real points.
+     trip 1   rows k1 = 0 ... L1 / 2 of the half spectrum read as [L2][L1]: Y[k2] = X[k1 + L1 k2] below L2 / 2, the
+              conjugate of X[(L1 - k1) + L1 (L2 - 1 - k2)] above (every index stays within 0 ... n / 2), backward DFT
+              of length L2 along the row, twiddle w_n^(+k1 j2) on the output, and the rows k1 and L1 - k1 of the
+              scratch image Z[k1][c] = A[k1][2c] + i A[k1][2c + 1] stored from the one result (A[L1 - k1] = conj A[k1])
+              (FFTW_AMD_F_REAL_DEC_C2R, pass3t_kernel RD = 2)
+     trip 2   the plain backward complex pass of length L1 down the columns of Z, which leaves the pairs
+              (x[j1 L2 + 2c], x[j1 L2 + 2c + 1]) in the real output
+   The three-trip plans are tangle + two passes.  Z has the r2c plan's layout (plain row-major), so trip 2 is that
+   plan's trip 1 run the other way and trip 1 stores 64-byte runs, four pairs of a row per quarter wave.
+   MEASURED (tools/perf/perf_c2r_two_trip.py, profiles/r04_c2r_two_trip.txt; ms per 4 GiB of output, median of 9, two chunk
+   lanes, against the three-trip plan of the same binary): 2^22 4.33 against 4.17 (a tie: the ranges overlap), 2^21 3.56
+   against 4.08, 2^20 3.51 against 4.14.  Per step the rows trip takes 1.7 ... 2.6 x the column pass (2^22: 5.58 and 3.22 ms
+   summed over the chunks of both lanes): its 64-byte store runs are the next lever; neither remedy (a stage-C owner map
+   with d1 fastest, a scratch layout blocked in c) has been built or measured.  Off under
+   FFTW_ESTIMATE like its twin (cfg.real_dec, FFTW_AMD_REAL_DEC=1), a candidate of the FFTW_MEASURE search for c2r
+   problems, remembered by wisdom through the same bit.  r2r problems whose inner transform is a c2r keep their plans
+   (no prologue / epilogue fusion here).  The plan never writes its input.  Reference counterpart: ct_hc2c backward
+   (fftw/fftw_api.c:5551-5603, fftw/rdft_scalar/r2cb/hc2cbdft_*.c).  The first step has no fallback executor, so
+   everything it needs is settled here.  1 = emitted. */
+static int emit_c2r_decimated(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, fa_loc out) {
+    fa_axis ax = *axp, c_ax, lay;
+    const i64 L2 = 2048;
+    i64 L1, h = nl / 2, zts, lts[FA_MAXLOOPS + 1], total;
+    int zbuf, j, nd, cloop, n0 = p->nsteps;
+    double flops0 = p->est_flops;
+    fa_loc z;
+    sdim d[FA_MAXLOOPS + 1];
+    fftw_amd_step_desc *s;
+    if (!p->cfg.real_dec || p->type != FA_C2R || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_NARROW") ||
+        (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
+        return 0;
+    if (nl % L2 || !fa_hip_r3tw_cdec((int)L2) || fa_hip_r3t_tile((int)L2) < 8) return 0;
+    L1 = nl / L2;
+    if (L1 % 2 || L1 < 256) return 0;
+    /* trip 2 must be ONE strided pass: a register kernel of that length with 128-byte segments */
+    if (!((L1 <= 1024 && has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
+    if (ax.nloops >= FA_MAXLOOPS || cur.im != 1 || out.im != 0) return 0;
+    if ((cur.base % 2) || (out.base % 2) || (cur.buf < 2 && ((size_t)p->ri % 16)) || ((size_t)p->ro % 16)) return 0;
+    for (j = 0; j < ax.nloops; ++j)
+        if ((ax.loops[j].is % 2) || (ax.loops[j].os % 2)) return 0;
+
+    lay = ax;
+    lay.is = 1;
+    total = scratch_layout(&lay, h, &zts, lts);
+    zbuf = buf_acquire(p, total);
+    z.buf = zbuf; z.base = 0; z.im = 1;
+
+    nd = 0;
+    d[nd].n = L1 / 2 + 1; d[nd].is = 2; d[nd].os = (L2 / 2) * zts; d[nd].tw = 1; d[nd].is_batch = 0; ++nd;
+    for (j = 0; j < ax.nloops; ++j) {
+        d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = lts[j];
+        d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
+    }
+    emit_pass(p, cur, z, L2, 2 * L1, zts, d, nd, nl, FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_DEC_C2R);
+    if (p->failed) goto undo;
+    s = &p->steps[p->nsteps - 1];
+    if (s->variant != FFTW_AMD_K_R3 || s->tile != fa_hip_r3t_tile((int)L2) || s->tile_lo_n != 1 ||
+        s->dim_n[0] != L1 / 2 + 1 || s->dim_tw[0] != 1 || s->batch_dim == 0)
+        goto undo;
+
+    c_ax = ax;
+    cloop = c_ax.nloops++;
+    c_ax.loops[cloop].n = L2 / 2;
+    c_ax.loops[cloop].is = zts;
+    c_ax.loops[cloop].os = 2;
+    for (j = 0; j < ax.nloops; ++j) c_ax.loops[j].is = lts[j];
+    c_ax.n = L1;
+    c_ax.is = (L2 / 2) * zts;
+    c_ax.os = L2;                      /* L2 / 2 pairs of two doubles */
+    c_ax.src = z;
+    c_ax.dst = out;
+    c_ax.dst.im = 1;                   /* imaginary part = odd sample */
+    c_ax.dense = 0;
+    c_ax.flags_in = FFTW_AMD_F_SWAP_IN;
+    c_ax.flags_out = FFTW_AMD_F_SWAP_OUT;
+    fa_emit_axis(p, &c_ax);
+    if (p->failed || p->nsteps != n0 + 2) goto undo;
+    buf_release(p, zbuf);
+    return 1;
+undo:
+    if (p->failed) return 1;
+    p->nsteps = n0;
+    p->est_flops = flops0;
+    buf_release(p, zbuf);
+    return 0;
+}
+
 static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 cs, fa_loc out, i64 rs, int pro,
                           i64 ps, i64 pim, int post) {
     fa_axis ax = *axp;
     int j;
     if (ps == 0) { ps = 2 * rs; pim = rs; }
+    if (pro == 0 && post == 0 && ps == 2 && pim == 1 && cs == 2 && emit_c2r_decimated(p, nl, &ax, cur, out)) return;
     if (nl % 4 == 0 && nl >= 8 && ax.nloops < FA_MAXLOOPS && !getenv("FFTW_AMD_NO_RADIX4") &&
         ((axis_pass_count(p, nl / 4) < half_axis_pass_count(p, nl / 2) && radix4_passes_have_kernels(p, nl / 4)) ||
          getenv("FFTW_AMD_FORCE_RADIX4"))) {
@@ -2998,6 +3087,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_P1024) sapp(s, cap, &len, "reg32x32");
             else if (d->variant == FFTW_AMD_K_RR) sapp(s, cap, &len, "reg2");
             else if (d->variant == FFTW_AMD_K_R3 && (d->flags & FFTW_AMD_F_REAL_DEC)) sapp(s, cap, &len, "reg3+real-decimated");
+            else if (d->variant == FFTW_AMD_K_R3 && (d->flags & FFTW_AMD_F_REAL_DEC_C2R)) sapp(s, cap, &len, "reg3+c2r-decimated");
             else if (d->variant == FFTW_AMD_K_R3) sapp(s, cap, &len, (d->flags & FFTW_AMD_F_LO_DFT) ? (d->tile_lo_n == 4 ? "reg3+dft4-across-rows" : "reg3+dft2-across-rows") : "reg3");
             else if (d->variant == FFTW_AMD_K_R1) sapp(s, cap, &len, "reg1");
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);

@@ -368,10 +368,27 @@ enum {
                                       k1 dim_os[0] + k2 os_l, the others conjugated to (L1-k1) dim_os[0] + (L-1-k2) os_l
                                       (not for k1 = 0 and L1 / 2, whose second halves repeat their first; X[n / 2] comes from
                                       row 0).  No fallback executor: planned only for aligned interleaved arrays */
-    FFTW_AMD_F_PAIR_SWAP = 1 << 16 /* transposition step (FFTW_AMD_K_TRANSPOSE) of a square matrix onto itself (source and
+    FFTW_AMD_F_PAIR_SWAP = 1 << 16,/* transposition step (FFTW_AMD_K_TRANSPOSE) of a square matrix onto itself (source and
                                       destination are the same array, equal leading dimensions): workgroups exchange the tile
                                       pairs (ti, tj) / (tj, ti) in place, no scratch.  As for every copy, all reads happen
                                       before any write of the same word */
+    FFTW_AMD_F_REAL_DEC_C2R = 1 << 17 /* pass: the FIRST trip of a two-trip c2r transform of n = L1 x L real points (pass3t_kernel,
+                                      RD = 2), the backward twin of FFTW_AMD_F_REAL_DEC.  The source is the half spectrum
+                                      X[0 ... n / 2], entry k at k1 dim_is[0] + k2 is_l for k = k1 + L1 k2 (so is_l = L1 dim_is[0]).
+                                      The tile dim runs over the rows k1 = 0 ... L1 / 2 (dim_n[0] = L1 / 2 + 1, dim_tw[0] = 1).
+                                      Row k1 is loaded as Y[k2] = X[k1 + L1 k2] for k2 < L / 2 and
+                                      Y[k2] = conj X[(L1 - k1) + L1 (L - 1 - k2)] for k2 >= L / 2, the imaginary parts of X[0] and
+                                      X[n / 2] read as 0; it is transformed backward (the step carries FFTW_AMD_F_SWAP_IN and
+                                      _SWAP_OUT like every backward pass) and multiplied by the twiddle on the OUTPUT index:
+                                      A[k1][j2] = w_n^(+k1 j2) sum_k2 Y[k2] w_L^(+k2 j2).  The destination is the scratch image
+                                      Z of L1 rows (at dim_os[0]) of L / 2 complex pairs (at os_l), plain row-major:
+                                      Z[k1][c] = A[k1][2c] + i A[k1][2c+1] and, for 0 < k1 < L1 / 2,
+                                      Z[L1-k1][c] = conj A[k1][2c] + i conj A[k1][2c+1]; the rows k1 = 0 and L1 / 2 are their own
+                                      mirrors and store Z[k1][c] = Re A[k1][2c] + i Re A[k1][2c+1] only.  Every word of the rows
+                                      0 ... L1 - 1 is written once, nothing else is, and the source is never written.  The
+                                      backward complex pass of length L1 down the columns of Z then leaves the pairs
+                                      (x[j1 L + 2c], x[j1 L + 2c + 1]).  No fallback executor: planned only for aligned
+                                      interleaved arrays */
 };
 
 int fftw_amd_plan_num_steps(const fftw_plan p);
