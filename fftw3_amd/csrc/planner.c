@@ -317,6 +317,11 @@ static fftw_amd_step_desc *new_step(plan *p, int kind) {
     return s;
 }
 
+static void step_set_locs(fftw_amd_step_desc *s, fa_loc src, fa_loc dst) {
+    s->src_buf = src.buf; s->src_base = src.base; s->src_im = src.im;
+    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = dst.im;
+}
+
 typedef struct { i64 n, is, os, tw; int is_batch; } sdim;
 
 /* put dims into the step; returns -1 if they do not fit */
@@ -416,8 +421,7 @@ static void emit_pass(plan *p, fa_loc src, fa_loc dst, i64 L, i64 is_l, i64 os_l
             best = nb;
         }
     }
-    s->src_buf = src.buf; s->src_base = src.base; s->src_im = src.im;
-    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = dst.im;
+    step_set_locs(s, src, dst);
     s->flags = flags;
     s->L = (int)L;
     s->is_l = is_l;
@@ -493,8 +497,7 @@ static void emit_copy(plan *p, int kind, fa_loc src, fa_loc dst, i64 K, i64 Kval
                       i64 is_k, i64 os_k, const sdim *dims, int nd, int flags,
                       int table, int table2) {
     fftw_amd_step_desc *s = new_step(p, kind);
-    s->src_buf = src.buf; s->src_base = src.base; s->src_im = src.im;
-    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = dst.im;
+    step_set_locs(s, src, dst);
     s->flags = flags;
     s->is_l = is_k;
     s->os_l = os_k;
@@ -579,8 +582,8 @@ int fa_transp_inplace_ok(const fa_transp *t) {
 static void emit_transpose(plan *p, fa_loc src, fa_loc dst, const fa_transp *t, i64 unit, int inplace) {
     fftw_amd_step_desc *s = new_step(p, FFTW_AMD_STEP_COPY);
     int i;
-    s->src_buf = src.buf; s->src_base = src.base; s->src_im = unit == 2 ? 1 : 0;
-    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = unit == 2 ? 1 : 0;
+    src.im = dst.im = unit == 2 ? 1 : 0;
+    step_set_locs(s, src, dst);
     s->flags = (unit == 1 ? (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT) : 0) | (inplace ? FFTW_AMD_F_PAIR_SWAP : 0);
     s->is_l = s->os_l = unit;
     s->aux_n = s->aux_valid = t->vl / unit;
@@ -609,12 +612,15 @@ static int transp_layout_ok(const plan *p, fa_loc src, fa_loc dst) {
 static void fa_emit_axis(plan *p, const fa_axis *ax);
 static int has_register_kernel(i64 L);
 
-static int loops_to_sdims(const fa_axis *ax, sdim *d, int use_dst_as_src) {
+/* the loops of an axis as step dims d[0 ... nloops); lis / los: the loop strides on the two sides when a side is a
+   scratch image, NULL = the axis's own .is / .os.  Returns the count, so a caller that put nd dims of its own first
+   (a twiddled one, say) appends with nd += loop_sdims(..., d + nd). */
+static int loop_sdims(const fa_axis *ax, const i64 *lis, const i64 *los, sdim *d) {
     int i;
     for (i = 0; i < ax->nloops; ++i) {
         d[i].n = ax->loops[i].n;
-        d[i].is = use_dst_as_src ? ax->loops[i].os : ax->loops[i].is;
-        d[i].os = ax->loops[i].os;
+        d[i].is = lis ? lis[i] : ax->loops[i].is;
+        d[i].os = los ? los[i] : ax->loops[i].os;
         d[i].tw = 0;
         d[i].is_batch = (i == ax->batch_loop);
     }
@@ -657,8 +663,15 @@ static i64 scratch_layout_u(const fa_axis *ax, i64 n_axis, i64 unit, i64 *ts_axi
     return stride;
 }
 
-static i64 scratch_layout(const fa_axis *ax, i64 n_axis, i64 *ts_axis, i64 *ts_loop) {
-    return scratch_layout_u(ax, n_axis, 2, ts_axis, ts_loop);
+/* A scratch image of n_axis complex numbers per sequence over the loops of `ax`, acquired: its location, axis stride
+   *ts and loop strides lts[].  axis_key ranks the axis among the loops' source strides: 1 = the axis innermost.
+   The caller releases it: buf_release(p, z.buf). */
+static fa_loc scratch_image(plan *p, const fa_axis *ax, i64 axis_key, i64 n_axis, i64 *ts, i64 *lts) {
+    fa_axis lay = *ax;
+    fa_loc z = { 0, 0, 1 };
+    lay.is = axis_key;
+    z.buf = buf_acquire(p, scratch_layout_u(&lay, n_axis, 2, ts, lts));
+    return z;
 }
 
 /* Cooley-Tukey over k >= 2 passes through a scratch image:
@@ -667,10 +680,10 @@ static i64 scratch_layout(const fa_axis *ax, i64 n_axis, i64 *ts_axis, i64 *ts_l
    written transposed so the output is in natural order. */
 static void emit_ct(plan *p, const fa_axis *ax, const i64 *lens, int k) {
     i64 M[FA_MAXPASS + 1], Pf[FA_MAXPASS + 1];
-    i64 ts, lts[FA_MAXLOOPS], total;
+    i64 ts, lts[FA_MAXLOOPS];
     sdim d[FFTW_AMD_MAX_DIMS + FA_MAXLOOPS];
     fa_loc tmp;
-    int i, j, nd, tbuf;
+    int i, j, nd;
 
     /* M[i] = product of the lengths after pass i, Pf[i] = product before it */
     M[k - 1] = 1;
@@ -678,11 +691,7 @@ static void emit_ct(plan *p, const fa_axis *ax, const i64 *lens, int k) {
     Pf[0] = 1;
     for (i = 1; i < k; ++i) Pf[i] = Pf[i - 1] * lens[i - 1];
 
-    total = scratch_layout(ax, ax->n, &ts, lts);
-    tbuf = buf_acquire(p, total);
-    tmp.buf = tbuf;
-    tmp.base = 0;
-    tmp.im = 1;
+    tmp = scratch_image(p, ax, ax->is, ax->n, &ts, lts);
 
     for (i = 0; i < k; ++i) {
         int flags = 0;
@@ -690,10 +699,7 @@ static void emit_ct(plan *p, const fa_axis *ax, const i64 *lens, int k) {
         if (i == 0) {
             /* source -> scratch */
             d[nd].n = M[0]; d[nd].is = ax->is; d[nd].os = ts; d[nd].tw = 1; d[nd].is_batch = 0; ++nd;
-            for (j = 0; j < ax->nloops; ++j) {
-                d[nd].n = ax->loops[j].n; d[nd].is = ax->loops[j].is; d[nd].os = lts[j];
-                d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-            }
+            nd += loop_sdims(ax, NULL, lts, d + nd);
             flags = ax->flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN);
             /* two passes: the twiddle w_n^(k_0 j) is applied by the last pass on
                its input (index j along the row, k_0 = which row) */
@@ -706,10 +712,7 @@ static void emit_ct(plan *p, const fa_axis *ax, const i64 *lens, int k) {
                 d[nd].n = lens[j]; d[nd].is = M[j] * ts; d[nd].os = M[j] * ts;
                 d[nd].tw = 0; d[nd].is_batch = 0; ++nd;
             }
-            for (j = 0; j < ax->nloops; ++j) {
-                d[nd].n = ax->loops[j].n; d[nd].is = lts[j]; d[nd].os = lts[j];
-                d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-            }
+            nd += loop_sdims(ax, lts, lts, d + nd);
             emit_pass(p, tmp, tmp, lens[i], M[i] * ts, M[i] * ts, d, nd, lens[i] * M[i], 0);
         } else {
             /* scratch -> destination, digits reversed into natural order */
@@ -717,45 +720,29 @@ static void emit_ct(plan *p, const fa_axis *ax, const i64 *lens, int k) {
                 d[nd].n = lens[j]; d[nd].is = M[j] * ts; d[nd].os = Pf[j] * ax->os;
                 d[nd].tw = (k == 2) ? 1 : 0; d[nd].is_batch = 0; ++nd;
             }
-            for (j = 0; j < ax->nloops; ++j) {
-                d[nd].n = ax->loops[j].n; d[nd].is = lts[j]; d[nd].os = ax->loops[j].os;
-                d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-            }
+            nd += loop_sdims(ax, lts, NULL, d + nd);
             flags = ax->flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT);
             if (k == 2) flags |= FFTW_AMD_F_TW_IN;
             emit_pass(p, tmp, ax->dst, lens[k - 1], ts, Pf[k - 1] * ax->os, d, nd,
                       k == 2 ? ax->n : 0, flags);
         }
     }
-    buf_release(p, tbuf);
+    buf_release(p, tmp.buf);
 }
 
 /* Bluestein: y[k] = conj(w_k) * ( (x conj(w)) (*) w )[k], the convolution by
    two DFTs of the smooth size nb >= 2n-1  (reference A.c:1642-1688) */
 static void emit_bluestein(plan *p, const fa_axis *ax) {
     i64 n = ax->n, nb = fa_next_smooth(2 * n - 1);
-    i64 wts, lts[FA_MAXLOOPS], total;
+    i64 wts, lts[FA_MAXLOOPS];
     int chirp = tab_chirp(p, n, nb);
     int kern = tab_blue_kernel(p, n, nb);
-    int wbuf, j, nd;
-    fa_loc w;
+    int j, nd;
+    fa_loc w = scratch_image(p, ax, 1, nb, &wts, lts);     /* work image [loops][nb], axis innermost */
     sdim d[FA_MAXLOOPS];
     fa_axis sub;
 
-    /* work image [loops][nb], axis innermost */
-    {
-        fa_axis lay = *ax;
-        lay.is = 1;   /* force the axis innermost in the scratch */
-        total = scratch_layout(&lay, nb, &wts, lts);
-    }
-    wbuf = buf_acquire(p, total);
-    w.buf = wbuf; w.base = 0; w.im = 1;
-
-    nd = 0;
-    for (j = 0; j < ax->nloops; ++j) {
-        d[nd].n = ax->loops[j].n; d[nd].is = ax->loops[j].is; d[nd].os = lts[j];
-        d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-    }
+    nd = loop_sdims(ax, NULL, lts, d);
     emit_copy(p, FFTW_AMD_STEP_COPY, ax->src, w, nb, n, ax->is, wts, d, nd,
               (ax->flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN)) | FFTW_AMD_F_MUL_CONJ,
               chirp, -1);
@@ -779,36 +766,23 @@ static void emit_bluestein(plan *p, const fa_axis *ax) {
     emit_copy(p, FFTW_AMD_STEP_COPY, w, ax->dst, n, n, wts, ax->os, d, nd,
               (ax->flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT)) | FFTW_AMD_F_MUL_CONJ,
               chirp, -1);
-    buf_release(p, wbuf);
+    buf_release(p, w.buf);
 }
 
 /* Rader for a prime p: a cyclic convolution of length p-1 over the
    multiplicative group (reference rader_apply A.c:4187-4261) */
 static void emit_rader(plan *p, const fa_axis *ax) {
     i64 pr = ax->n, m = pr - 1;
-    i64 wts, lts[FA_MAXLOOPS], xts, xlts[FA_MAXLOOPS], total, xtotal;
+    i64 wts, lts[FA_MAXLOOPS], xts, xlts[FA_MAXLOOPS];
     int pf = tab_perm(p, pr, 0), pinv = tab_perm(p, pr, 1);
     int omega = tab_rader_kernel(p, pr);
-    int wbuf, xbuf, j, nd;
-    fa_loc w, x0;
+    int j, nd;
+    fa_loc w = scratch_image(p, ax, 1, m, &wts, lts), x0 = scratch_image(p, ax, 1, 1, &xts, xlts);
     sdim d[FA_MAXLOOPS];
-    fa_axis sub, lay;
+    fa_axis sub;
     fftw_amd_step_desc *s;
 
-    lay = *ax;
-    lay.is = 1;
-    total = scratch_layout(&lay, m, &wts, lts);
-    xtotal = scratch_layout(&lay, 1, &xts, xlts);
-    wbuf = buf_acquire(p, total);
-    xbuf = buf_acquire(p, xtotal);
-    w.buf = wbuf; w.base = 0; w.im = 1;
-    x0.buf = xbuf; x0.base = 0; x0.im = 1;
-
-    nd = 0;
-    for (j = 0; j < ax->nloops; ++j) {
-        d[nd].n = ax->loops[j].n; d[nd].is = ax->loops[j].is; d[nd].os = lts[j];
-        d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-    }
+    nd = loop_sdims(ax, NULL, lts, d);
     /* a[k] = x[g^k] */
     emit_copy(p, FFTW_AMD_STEP_COPY, ax->src, w, m, m, ax->is, wts, d, nd,
               (ax->flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN)) | FFTW_AMD_F_PERM_SRC,
@@ -829,9 +803,8 @@ static void emit_rader(plan *p, const fa_axis *ax) {
     /* pointwise product, DC fix-ups, Y[0].  The kernel walks vectors in the
        scratch order, which is the order of dims given here. */
     s = new_step(p, FFTW_AMD_STEP_RADER_MUL);
-    s->src_buf = wbuf; s->src_base = 0; s->src_im = 1;
-    s->dst_buf = ax->dst.buf; s->dst_base = ax->dst.base; s->dst_im = ax->dst.im;
-    s->aux_buf = xbuf; s->aux_base = 0;
+    step_set_locs(s, w, ax->dst);
+    s->aux_buf = x0.buf; s->aux_base = 0;
     s->aux_n = m;
     s->table = omega;
     s->flags = ax->flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT);
@@ -863,8 +836,8 @@ static void emit_rader(plan *p, const fa_axis *ax) {
     emit_copy(p, FFTW_AMD_STEP_COPY, w, ax->dst, m, m, wts, ax->os, d, nd,
               (ax->flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT)) | FFTW_AMD_F_PERM_DST,
               -1, pinv);
-    buf_release(p, xbuf);
-    buf_release(p, wbuf);
+    buf_release(p, x0.buf);
+    buf_release(p, w.buf);
 }
 
 /* lengths with a register kernel (pass1024 / passrr) */
@@ -1042,7 +1015,7 @@ static int long_rows_ok(const plan *p, const fa_axis *ax) {
    apply (long_rows_ok).  1 = emitted. */
 static int emit_bluestein_rows(plan *p, const fa_axis *ax) {
     i64 need = 2 * ax->n - 1;
-    int nb, j, nd = 0;
+    int nb, j;
     sdim d[FA_MAXLOOPS];
     fftw_amd_step_desc *s;
     if (getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_3S") || getenv("FFTW_AMD_NO_BLUE_ROWS")) return 0;
@@ -1050,11 +1023,7 @@ static int emit_bluestein_rows(plan *p, const fa_axis *ax) {
     nb = fa_hip_blue_nb((int)need);
     if (nb <= 0 || (double)nb > 1.35 * (double)need) return 0;
     if (!long_rows_ok(p, ax)) return 0;
-    for (j = 0; j < ax->nloops; ++j) {
-        d[nd].n = ax->loops[j].n; d[nd].is = ax->loops[j].is; d[nd].os = ax->loops[j].os;
-        d[nd].tw = 0; d[nd].is_batch = (j == ax->batch_loop); ++nd;
-    }
-    emit_pass(p, ax->src, ax->dst, nb, 2, 2, d, nd, 0,
+    emit_pass(p, ax->src, ax->dst, nb, 2, 2, d, loop_sdims(ax, NULL, NULL, d), 0,
               (ax->flags_in & FFTW_AMD_F_SWAP_IN) | (ax->flags_out & FFTW_AMD_F_SWAP_OUT));
     if (p->failed) return 1;
     s = &p->steps[p->nsteps - 1];
@@ -1234,7 +1203,7 @@ static void fa_emit_axis(plan *p, const fa_axis *ax_in) {
         return;
     }
     if (k == 1) {
-        int nd = loops_to_sdims(&ax, d, 0);
+        int nd = loop_sdims(&ax, NULL, NULL, d);
         emit_pass(p, ax.src, ax.dst, ax.n, ax.is, ax.os, d, nd, 0,
                   (ax.flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN)) |
                   (ax.flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT)));
@@ -1386,7 +1355,7 @@ static void emit_loops_copy(plan *p, fa_loc src, fa_loc dst, int contig_k) {
     }
     memset(&ax, 0, sizeof(ax));
     if (collect_loops(p, p->dims, p->rank, -1, NULL, 0, &ax)) { p->failed = 1; return; }
-    nd = loops_to_sdims(&ax, d, 0);
+    nd = loop_sdims(&ax, NULL, NULL, d);
     if (unit == 2) { emit_pass(p, src, dst, 1, 0, 0, d, nd, 0, 0); return; }
     if (contig_k) {
         /* a loop that is contiguous on both sides becomes the copy's own index: copy_kernel then gives a workgroup 256
@@ -1517,16 +1486,6 @@ static int half_axis_pass_count(const plan *p, i64 n) {
     return axis_pass_count(p, n);
 }
 
-/* r2c: last dim real -> half spectrum, then complex DFTs over the other dims
-   on the half-spectrum array (reference rank_geq2_rdft2 A.c:10111-10282).
-   p->dims[].is are strides of the REAL array (doubles), .os of the complex
-   array (doubles, so 2 per complex). */
-/* real -> half spectrum along one axis.  ax: the loops (.is = strides in the real
-   source, .os = strides in the complex destination) and the batch loop; rs / cs:
-   element strides of the transform index on the two sides, in doubles. */
-/* the fused rows kernel loads 16-byte pairs and stores 16-byte complex numbers: every
-   loop stride must keep that alignment, the user arrays must be 16-byte aligned, there must
-   be a loop to tile over, and the tile dim must not be a two-level (pair) dim */
 /* Do source and destination of a one-trip rows step alias?  The fused rows kernels read a tile
    of rows and write the same tile's results without a scratch image in between, so when both
    sides are the same user memory every row must map onto itself (FFTW's padded in-place
@@ -1545,36 +1504,25 @@ static int rows_alias_ok(const plan *p, const fa_axis *ax, fa_loc a, fa_loc b) {
     return 1;
 }
 
-static int r2c_rows_layout_ok(const plan *p, const fa_axis *ax, fa_loc in, fa_loc out, int epi, int pre) {
+/* the fused rows kernel loads 16-byte pairs and stores 16-byte complex numbers: every
+   loop stride must keep that alignment, the user arrays must be 16-byte aligned, there must
+   be a loop to tile over, and the tile dim must not be a two-level (pair) dim.
+   hook_in / hook_out: an r2r prologue on the source / epilogue on the destination side (FFTW_AMD_R2R_*, 0 = none):
+   that side is then the user's real array of any stride, which the kernel gathers from / scatters to by element */
+static int real_rows_layout_ok(const plan *p, const fa_axis *ax, fa_loc src, fa_loc dst, int hook_in, int hook_out) {
     int j, rows = 0;
     if (getenv("FFTW_AMD_NO_R2CROWS")) return 0;
-    if (!rows_alias_ok(p, ax, in, out)) return 0;
+    if (!rows_alias_ok(p, ax, src, dst)) return 0;
     for (j = 0; j < ax->nloops; ++j) {
-        if ((!pre && (ax->loops[j].is % 2)) || (!epi && (ax->loops[j].os % 2))) return 0;
+        if ((!hook_in && (ax->loops[j].is % 2)) || (!hook_out && (ax->loops[j].os % 2))) return 0;
         /* emit_pass would fold such a loop into a two-level tile dim, which this kernel lacks */
         if (ax->loops[j].n == 2 && (iabs(ax->loops[j].is) == 2 || iabs(ax->loops[j].os) == 2)) return 0;
         if (ax->loops[j].n > 1) rows = 1;
     }
     if (!rows) return 0;
-    if (!pre && in.buf == 0 && (((size_t)p->ri % 16) || (in.base % 2))) return 0;
-    if (!epi && out.buf == 1 && (((size_t)p->ro % 16) || (out.base % 2))) return 0;
-    if (!pre && in.buf == 1 && (((size_t)p->ro % 16) || (in.base % 2))) return 0;
-    return 1;
-}
-
-static int c2r_rows_layout_ok(const plan *p, const fa_axis *ax, fa_loc cur, fa_loc out, int pro, int post) {
-    int j, rows = 0;
-    if (getenv("FFTW_AMD_NO_R2CROWS")) return 0;
-    if (!rows_alias_ok(p, ax, cur, out)) return 0;
-    for (j = 0; j < ax->nloops; ++j) {
-        if ((!pro && (ax->loops[j].is % 2)) || (!post && (ax->loops[j].os % 2))) return 0;
-        if (ax->loops[j].n == 2 && (iabs(ax->loops[j].is) == 2 || iabs(ax->loops[j].os) == 2)) return 0;
-        if (ax->loops[j].n > 1) rows = 1;
-    }
-    if (!rows) return 0;
-    if (!pro && cur.buf == 0 && (((size_t)p->ri % 16) || (cur.base % 2))) return 0;
-    if (!pro && cur.buf == 1 && (((size_t)p->ro % 16) || (cur.base % 2))) return 0;
-    if (!post && out.buf == 1 && (((size_t)p->ro % 16) || (out.base % 2))) return 0;
+    if (!hook_in && src.buf == 0 && (((size_t)p->ri % 16) || (src.base % 2))) return 0;
+    if (!hook_in && src.buf == 1 && (((size_t)p->ro % 16) || (src.base % 2))) return 0;
+    if (!hook_out && dst.buf == 1 && (((size_t)p->ro % 16) || (dst.base % 2))) return 0;
     return 1;
 }
 
@@ -1609,23 +1557,142 @@ static int short_real_rows_tile(const fa_axis *ax, i64 half, int hooks, int fwd)
     return 0;
 }
 
+/* rows per tile of the one-trip rows step of an r2c (fwd) / c2r axis, 0: no such kernel */
+static int real_rows_tile_for(const fa_axis *ax, i64 half, int hooks, int fwd) {
+    const int t = short_real_rows_tile(ax, half, hooks, fwd);
+    return t > 0 ? t : real_rows_tile(half, hooks);
+}
+
 /* can the r2c / c2r axis emitters fuse an r2r epilogue / prologue for this length? */
 static int r2r_can_fuse(i64 nl) { return nl >= 2 && nl % 2 == 0 && !getenv("FFTW_AMD_R2R_UNFUSED"); }
 
-/* twiddle tables of an untangle / tangle step.  Plain: modulus nl.  With a fused
-   REDFT/RODFT 10/01 epilogue or prologue: the modulus-4n table serves both the
-   r2r twiddle w_4n^k and the untangle twiddle w_n^k = w_4n^(4k) (step.tile = 4 is
-   the index multiplier of the latter). */
+/* Twiddle tables of a step that untangles / tangles a real transform of nl points.  Plain: modulus nl.  With a fused
+   REDFT/RODFT 10/01 epilogue or prologue: the modulus-4n table serves both the r2r twiddle w_4n^k and the untangle
+   twiddle w_n^k = w_4n^(4k); *mult is the index multiplier of the latter.  `sets` names the fused modes the caller
+   takes for such: the untangle / tangle steps all four, a forward rows step the epilogues, a backward one the
+   prologues. */
+enum { TW4_POST10 = 1, TW4_PRE01 = 2 };
+static void real_tw_tables(plan *p, fftw_amd_step_desc *s, i64 nl, int mode, int sets, i64 *mult) {
+    const int four = ((sets & TW4_POST10) && (mode == FFTW_AMD_R2R_POST_E10 || mode == FFTW_AMD_R2R_POST_O10)) ||
+                     ((sets & TW4_PRE01) && (mode == FFTW_AMD_R2R_PRE_E01 || mode == FFTW_AMD_R2R_PRE_O01));
+    *mult = four ? 4 : 1;
+    tab_tw2(p, *mult * nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
+}
+
+/* an untangle / tangle step with the fused r2r mode `mode` (0: none): step.variant = mode, step.tile = multiplier */
 static void r2r_fuse_tables(plan *p, fftw_amd_step_desc *s, i64 nl, int mode) {
+    i64 mult;
     s->variant = mode;
-    if (mode == FFTW_AMD_R2R_POST_E10 || mode == FFTW_AMD_R2R_POST_O10 ||
-        mode == FFTW_AMD_R2R_PRE_E01 || mode == FFTW_AMD_R2R_PRE_O01) {
-        tab_tw2(p, 4 * nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-        s->tile = 4;
+    real_tw_tables(p, s, nl, mode, TW4_POST10 | TW4_PRE01, &mult);
+    s->tile = (int)mult;
+}
+
+/* Contiguous rows of a supported length: the half-length complex DFT and the untangle (fwd: r2crows.hpp) or the
+   tangle and the backward half-length DFT in ONE trip instead of a pass plus an untangle / tangle step.  ss / ds:
+   element strides of the real array a hook (real_rows_layout_ok) gathers from / scatters to.  The r2r mode fused
+   with the untangle / tangle goes to aux_valid, the one the kernel does while it gathers the row (forward:
+   FFTW_AMD_R2R_PRE_*) or stores it (backward: FFTW_AMD_R2R_POST_E01 / O01) to aux_buf; aux_n = n, aux_base = index
+   multiplier of the untangle twiddle (real_tw_tables). */
+static void emit_real_rows_step(plan *p, int fwd, i64 nl, const fa_axis *ax, fa_loc src, i64 ss, fa_loc dst, i64 ds,
+                                int hook_in, int hook_out, int tile) {
+    const int fused = fwd ? hook_out : hook_in, shuffle = fwd ? hook_in : hook_out;
+    sdim d[FA_MAXLOOPS];
+    fftw_amd_step_desc *s;
+    if (fwd) src.im = 1; else dst.im = 1;          /* the real row as pairs: odd sample = imaginary part */
+    emit_pass(p, src, dst, nl / 2, hook_in ? ss : 2, hook_out ? ds : 2, d, loop_sdims(ax, NULL, NULL, d), 0,
+              fwd ? FFTW_AMD_F_R2C_ROWS : FFTW_AMD_F_C2R_ROWS);
+    s = &p->steps[p->nsteps - 1];
+    s->variant = fwd ? FFTW_AMD_K_R2C : FFTW_AMD_K_C2R;
+    s->aux_buf = shuffle ? shuffle : -1;
+    s->tile = tile;
+    s->tile_lo_n = 1;
+    s->aux_n = nl;
+    s->aux_valid = fused;
+    real_tw_tables(p, s, nl, fused, fwd ? TW4_POST10 : TW4_PRE01, &s->aux_base);
+    p->est_flops += 8.0 * (double)(nl / 2);
+}
+
+/* the radix-4 plans of a real axis (n = 4m, two complex transforms of m points and a radix-4 untangle / tangle) are
+   chosen when m needs fewer passes than n / 2; FFTW_AMD_NO_RADIX4 / FFTW_AMD_FORCE_RADIX4 override */
+static int use_radix4_real(const plan *p, i64 nl, const fa_axis *ax) {
+    return nl % 4 == 0 && nl >= 8 && ax->nloops < FA_MAXLOOPS && !getenv("FFTW_AMD_NO_RADIX4") &&
+           ((axis_pass_count(p, nl / 4) < half_axis_pass_count(p, nl / 2) && radix4_passes_have_kernels(p, nl / 4)) ||
+            getenv("FFTW_AMD_FORCE_RADIX4"));
+}
+
+/* ---- what the two decimated plans below (emit_r2c_decimated, emit_c2r_decimated) share */
+
+#define FA_DEC_L2 2048      /* length of the rows trip */
+
+/* May the real axis of nl points run decimated (fwd: r2c, src real and dst complex; else c2r)?  Returns L1 = nl / L2,
+   the length of the column trip, or 0.  The rows step has no fallback executor, so everything it needs is settled
+   here: the kernel exists, the column trip is ONE strided pass, interleaved arrays, 16-byte alignment, even strides. */
+static i64 real_dec_geometry(const plan *p, i64 nl, const fa_axis *ax, fa_loc src, fa_loc dst, int fwd) {
+    const i64 L2 = FA_DEC_L2, L1 = nl / L2;
+    int j;
+    if (!p->cfg.real_dec || (!fwd && p->type != FA_C2R) || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_NARROW") ||
+        (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
+        return 0;
+    if (nl % L2 || !(fwd ? fa_hip_r3tw_rdec((int)L2) : fa_hip_r3tw_cdec((int)L2)) || fa_hip_r3t_tile((int)L2) < 8) return 0;
+    if (L1 % 2 || L1 < 256) return 0;
+    /* a register kernel of that length with 128-byte segments */
+    if (!((L1 <= 1024 && has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
+    if (ax->nloops >= FA_MAXLOOPS || src.im != (fwd ? 0 : 1) || dst.im != (fwd ? 1 : 0)) return 0;
+    if ((src.base % 2) || (dst.base % 2) || ((size_t)p->ro % 16)) return 0;
+    /* (a c2r source may be the scratch image of the leading dims) */
+    if ((fwd || src.buf < 2) && ((size_t)p->ri % 16)) return 0;
+    for (j = 0; j < ax->nloops; ++j)
+        if ((ax->loops[j].is % 2) || (ax->loops[j].os % 2)) return 0;
+    return L1;
+}
+
+/* The column trip: complex transforms of L1 points down the columns of the real array `real` read as [L1][L2 / 2]
+   pairs, into (fwd) or backward out of the scratch image z, whose L2 / 2 columns ride as one more loop. */
+static fa_axis real_dec_column_axis(const fa_axis *ax, i64 L1, fa_loc real, fa_loc z, i64 zts, const i64 *lts, int fwd) {
+    const i64 L2 = FA_DEC_L2;
+    fa_axis c = *ax;
+    const int cloop = c.nloops++;
+    int j;
+    real.im = 1;                       /* odd sample = imaginary part */
+    c.n = L1;
+    c.dense = 0;
+    c.loops[cloop].n = L2 / 2;
+    if (fwd) {
+        c.loops[cloop].is = 2;
+        c.loops[cloop].os = zts;
+        for (j = 0; j < ax->nloops; ++j) c.loops[j].os = lts[j];
+        c.is = L2;                     /* L2 / 2 pairs of two doubles */
+        c.os = (L2 / 2) * zts;
+        c.src = real;
+        c.dst = z;
+        c.flags_in = c.flags_out = 0;
     } else {
-        tab_tw2(p, nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-        s->tile = 1;
+        c.loops[cloop].is = zts;
+        c.loops[cloop].os = 2;
+        for (j = 0; j < ax->nloops; ++j) c.loops[j].is = lts[j];
+        c.is = (L2 / 2) * zts;
+        c.os = L2;
+        c.src = z;
+        c.dst = real;
+        c.flags_in = FFTW_AMD_F_SWAP_IN;
+        c.flags_out = FFTW_AMD_F_SWAP_OUT;
     }
+    return c;
+}
+
+/* is the step emitted last the rows trip as its kernel takes it: rows k1 = 0 ... L1 / 2 as the tile dim? */
+static int real_dec_rows_step_ok(const plan *p, i64 L1) {
+    const fftw_amd_step_desc *s = &p->steps[p->nsteps - 1];
+    return s->variant == FFTW_AMD_K_R3 && s->tile == fa_hip_r3t_tile(FA_DEC_L2) && s->tile_lo_n == 1 &&
+           s->dim_n[0] == L1 / 2 + 1 && s->dim_tw[0] == 1 && s->batch_dim != 0;
+}
+
+/* the end of both: 1 = emitted (or the plan failed); 0 = not this way, the steps emitted so far are taken back */
+static int real_dec_end(plan *p, int ok, int n0, double flops0, int zbuf) {
+    if (p->failed) return 1;
+    if (!ok) { p->nsteps = n0; p->est_flops = flops0; }
+    buf_release(p, zbuf);
+    return ok;
 }
 
 /* A long real transform in TWO trips (round 3): n = L1 x L2 real points, decimated over the real data itself
@@ -1645,73 +1712,32 @@ static void r2r_fuse_tables(plan *p, fftw_amd_step_desc *s, i64 nl, int mode) {
    rdft2 Cooley-Tukey plan over real-data codelets (ct_hc2c_direct_apply, fftw/fftw_api.c:5831, with
    fftw/rdft_scalar/r2cf/hc2cfdft_*.c).  The last step has no fallback executor, so everything it needs is settled
    here (aligned interleaved arrays, even strides).  1 = emitted. */
-static int emit_r2c_decimated(plan *p, i64 nl, const fa_axis *axp, fa_loc in, fa_loc out) {
-    fa_axis ax = *axp, c_ax, lay;
-    const i64 L2 = 2048;
-    i64 L1, h = nl / 2, zts, lts[FA_MAXLOOPS + 1], total;
-    int zbuf, j, nd, cloop, n0 = p->nsteps;
-    double flops0 = p->est_flops;
+static int emit_r2c_decimated(plan *p, i64 nl, const fa_axis *ax, fa_loc in, fa_loc out) {
+    const i64 L2 = FA_DEC_L2, L1 = real_dec_geometry(p, nl, ax, in, out, 1);
+    const int n0 = p->nsteps;
+    const double flops0 = p->est_flops;
+    i64 zts, lts[FA_MAXLOOPS + 1];
+    fa_axis c_ax;
     fa_loc z;
     sdim d[FA_MAXLOOPS + 1];
-    fftw_amd_step_desc *s;
-    if (!p->cfg.real_dec || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_NARROW") ||
-        (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
-        return 0;
-    if (nl % L2 || !fa_hip_r3tw_rdec((int)L2) || fa_hip_r3t_tile((int)L2) < 8) return 0;
-    L1 = nl / L2;
-    if (L1 % 2 || L1 < 256) return 0;
-    /* trip 1 must be ONE strided pass: a register kernel of that length with 128-byte segments */
-    if (!((L1 <= 1024 && has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
-    if (ax.nloops >= FA_MAXLOOPS || in.im != 0 || out.im != 1) return 0;
-    if ((in.base % 2) || (out.base % 2) || ((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
-    for (j = 0; j < ax.nloops; ++j)
-        if ((ax.loops[j].is % 2) || (ax.loops[j].os % 2)) return 0;
-
-    lay = ax;
-    lay.is = 1;
-    total = scratch_layout(&lay, h, &zts, lts);
-    zbuf = buf_acquire(p, total);
-    z.buf = zbuf; z.base = 0; z.im = 1;
-
-    c_ax = ax;
-    cloop = c_ax.nloops++;
-    c_ax.loops[cloop].n = L2 / 2;
-    c_ax.loops[cloop].is = 2;
-    c_ax.loops[cloop].os = zts;
-    for (j = 0; j < ax.nloops; ++j) c_ax.loops[j].os = lts[j];
-    c_ax.n = L1;
-    c_ax.is = L2;                      /* L2 / 2 pairs of two doubles */
-    c_ax.os = (L2 / 2) * zts;
-    c_ax.src = in;
-    c_ax.src.im = 1;                   /* odd sample = imaginary part */
-    c_ax.dst = z;
-    c_ax.dense = 0;
-    c_ax.flags_in = c_ax.flags_out = 0;
+    int ok;
+    if (!L1) return 0;
+    z = scratch_image(p, ax, 1, nl / 2, &zts, lts);
+    c_ax = real_dec_column_axis(ax, L1, in, z, zts, lts, 1);
     fa_emit_axis(p, &c_ax);
-    if (p->failed || p->nsteps != n0 + 1) goto undo;
-
-    nd = 0;
-    d[nd].n = L1 / 2 + 1; d[nd].is = (L2 / 2) * zts; d[nd].os = 2; d[nd].tw = 1; d[nd].is_batch = 0; ++nd;
-    for (j = 0; j < ax.nloops; ++j) {
-        d[nd].n = ax.loops[j].n; d[nd].is = lts[j]; d[nd].os = ax.loops[j].os;
-        d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
+    ok = !p->failed && p->nsteps == n0 + 1;
+    if (ok) {
+        d[0].n = L1 / 2 + 1; d[0].is = (L2 / 2) * zts; d[0].os = 2; d[0].tw = 1; d[0].is_batch = 0;
+        emit_pass(p, z, out, L2, zts, 2 * L1, d, 1 + loop_sdims(ax, lts, NULL, d + 1), nl,
+                  FFTW_AMD_F_TW_IN | FFTW_AMD_F_REAL_DEC);
+        ok = !p->failed && real_dec_rows_step_ok(p, L1);
     }
-    emit_pass(p, z, out, L2, zts, 2 * L1, d, nd, nl, FFTW_AMD_F_TW_IN | FFTW_AMD_F_REAL_DEC);
-    if (p->failed) goto undo;
-    s = &p->steps[p->nsteps - 1];
-    if (s->variant != FFTW_AMD_K_R3 || s->tile != fa_hip_r3t_tile((int)L2) || s->tile_lo_n != 1 ||
-        s->dim_n[0] != L1 / 2 + 1 || s->dim_tw[0] != 1 || s->batch_dim == 0)
-        goto undo;
-    buf_release(p, zbuf);
-    return 1;
-undo:
-    if (p->failed) return 1;
-    p->nsteps = n0;
-    p->est_flops = flops0;
-    buf_release(p, zbuf);
-    return 0;
+    return real_dec_end(p, ok, n0, flops0, z.buf);
 }
 
+/* real -> half spectrum along one axis.  ax: the loops (.is = strides in the real
+   source, .os = strides in the complex destination) and the batch loop; rs / cs:
+   element strides of the transform index on the two sides, in doubles. */
 /* epi: 0 = store the half spectrum as complex numbers; FFTW_AMD_R2R_POST_* = the
    untangle step applies that r2r epilogue and writes reals of stride cs instead
    (even lengths only; returns 1 when the epilogue was fused, 0 when the caller
@@ -1723,33 +1749,27 @@ undo:
 static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs, fa_loc out, i64 cs, int epi,
                          i64 ps, i64 pim, int pre) {
     fa_axis ax = *axp;
-    i64 half = nl / 2 + 1;
-    int j;
+    i64 half = nl / 2 + 1, zts, lts[FA_MAXLOOPS + 1];
+    sdim d[FA_MAXLOOPS + 1];
+    fftw_amd_step_desc *s;
+    fa_loc z;
+    int j, nd, rows_tile;
     if (ps == 0) { ps = 2 * rs; pim = rs; }
     if (epi == 0 && pre == 0 && ps == 2 && pim == 1 && cs == 2 && emit_r2c_decimated(p, nl, &ax, in, out)) return 0;
-    if (nl % 4 == 0 && nl >= 8 && ax.nloops < FA_MAXLOOPS && !getenv("FFTW_AMD_NO_RADIX4") &&
-        ((axis_pass_count(p, nl / 4) < half_axis_pass_count(p, nl / 2) && radix4_passes_have_kernels(p, nl / 4)) ||
-         getenv("FFTW_AMD_FORCE_RADIX4"))) {
+    if (use_radix4_real(p, nl, &ax)) {
         /* n = 4m: two complex DFTs of size m on (x[4j], x[4j+1]) and (x[4j+2], x[4j+3]),
            then the radix-4 untangle -- the reference's rdft2-ct-dit/4 + hc2cfdft_4 plan,
            chosen when m needs fewer passes than n/2 (n = 2^22: m = 2^20 is 1024 x 1024) */
-        i64 m = nl / 4, zts, lts[FA_MAXLOOPS + 1], total;
-        int zbuf, nd, vloop;
-        fa_loc z;
+        i64 m = nl / 4;
         fa_axis q_ax = ax, lay;
-        sdim d[FA_MAXLOOPS + 1];
-        fftw_amd_step_desc *s;
         /* scratch [loops][v][m]: the vector index v rides as the innermost loop */
-        vloop = q_ax.nloops++;
+        int vloop = q_ax.nloops++;
         q_ax.loops[vloop].n = 2;
         q_ax.loops[vloop].is = ps;
         q_ax.loops[vloop].os = 0;
         lay = q_ax;
-        lay.is = 2;
         lay.loops[vloop].is = 1;           /* the pair index is innermost: Z[k][v], like the input */
-        total = scratch_layout(&lay, m, &zts, lts);
-        zbuf = buf_acquire(p, total);
-        z.buf = zbuf; z.base = 0; z.im = 1;
+        z = scratch_image(p, &lay, 2, m, &zts, lts);
         q_ax.dense = (pim == 1 && ps == 2);
         q_ax.n = m;
         q_ax.is = 2 * ps;
@@ -1761,72 +1781,27 @@ static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs,
         fa_emit_axis(p, &q_ax);
 
         s = new_step(p, FFTW_AMD_STEP_R2C_POST4);
-        s->src_buf = zbuf; s->src_base = 0; s->src_im = 1;
-        s->dst_buf = out.buf; s->dst_base = out.base; s->dst_im = out.im;
+        step_set_locs(s, z, out);
         s->is_l = zts;
         s->os_l = cs;
         s->aux_n = nl;
         s->aux_valid = lts[vloop];
         r2r_fuse_tables(p, s, nl, epi);
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = lts[j]; d[nd].os = ax.loops[j].os;
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
+        nd = loop_sdims(&ax, lts, NULL, d);
         s->kpos = order_dims_kpos(d, &nd, 1, cs);
         step_set_dims(p, s, d, nd, -1);
         p->est_flops += 20.0 * (double)m;
-        buf_release(p, zbuf);
+        buf_release(p, z.buf);
     } else if (nl % 2 == 0 && nl >= 2 && (pre != 0 || (ps == 2 && pim == 1)) &&
                (epi != 0 || (cs == 2 && out.im == 1)) &&
-               (short_real_rows_tile(&ax, nl / 2, epi || pre, 1) > 0 || real_rows_tile(nl / 2, epi || pre) > 0) &&
-               r2c_rows_layout_ok(p, &ax, in, out, epi, pre)) {
-        /* contiguous real rows of a supported length: the half-length complex DFT and the
-           untangle in ONE trip (r2crows.hpp) instead of a pass plus an untangle step */
-        sdim d[FA_MAXLOOPS];
-        int nd = 0;
-        fftw_amd_step_desc *s;
-        fa_loc src = in;
-        src.im = 1;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = ax.loops[j].os;
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
-        emit_pass(p, src, out, nl / 2, pre ? rs : 2, epi ? cs : 2, d, nd, 0, FFTW_AMD_F_R2C_ROWS);
-        s = &p->steps[p->nsteps - 1];
-        s->variant = FFTW_AMD_K_R2C;
-        s->aux_buf = pre ? pre : -1;     /* r2r pre-processing gathered inside the row (FFTW_AMD_R2R_PRE_*) */
-        s->tile = short_real_rows_tile(&ax, nl / 2, epi || pre, 1) > 0 ? short_real_rows_tile(&ax, nl / 2, epi || pre, 1)
-                                                                    : real_rows_tile(nl / 2, epi || pre);
-        s->tile_lo_n = 1;
-        /* aux_n = n, aux_valid = fused r2r epilogue (0: plain half spectrum), aux_base = index
-           multiplier of the untangle twiddle in the table (4 with the modulus-4n table of the
-           DCT-II / DST-II epilogues, see r2r_fuse_tables) */
-        s->aux_n = nl;
-        s->aux_valid = epi;
-        if (epi == FFTW_AMD_R2R_POST_E10 || epi == FFTW_AMD_R2R_POST_O10) {
-            tab_tw2(p, 4 * nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-            s->aux_base = 4;
-        } else {
-            tab_tw2(p, nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-            s->aux_base = 1;
-        }
-        p->est_flops += 8.0 * (double)(nl / 2);
-        return epi != 0;
+               (rows_tile = real_rows_tile_for(&ax, nl / 2, epi || pre, 1)) > 0 &&
+               real_rows_layout_ok(p, &ax, in, out, pre, epi)) {
+        emit_real_rows_step(p, 1, nl, &ax, in, rs, out, cs, pre, epi, rows_tile);
     } else if (nl % 2 == 0 && nl >= 2) {
         /* z[j] = x[2j] + i x[2j+1]; Z = DFT_{n/2}(z); untangle */
-        i64 h = nl / 2, zts, lts[FA_MAXLOOPS], total;
-        int zbuf, nd;
-        fa_loc z;
-        fa_axis half_ax = ax, lay;
-        sdim d[FA_MAXLOOPS];
-        fftw_amd_step_desc *s;
-        lay = ax;
-        lay.is = 1;
-        total = scratch_layout(&lay, h, &zts, lts);
-        zbuf = buf_acquire(p, total);
-        z.buf = zbuf; z.base = 0; z.im = 1;
-
+        i64 h = nl / 2;
+        fa_axis half_ax = ax;
+        z = scratch_image(p, &ax, 1, h, &zts, lts);
         half_ax.n = h;
         half_ax.is = ps;
         half_ax.os = zts;
@@ -1837,53 +1812,39 @@ static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs,
         fa_emit_axis(p, &half_ax);
 
         s = new_step(p, FFTW_AMD_STEP_R2C_POST);
-        s->src_buf = zbuf; s->src_base = 0; s->src_im = 1;
-        s->dst_buf = out.buf; s->dst_base = out.base; s->dst_im = out.im;
+        step_set_locs(s, z, out);
         s->is_l = zts;
         s->os_l = cs;
         s->aux_n = nl;
         r2r_fuse_tables(p, s, nl, epi);
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = lts[j]; d[nd].os = ax.loops[j].os;
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
+        nd = loop_sdims(&ax, lts, NULL, d);
         s->kpos = order_dims_kpos(d, &nd, 1, cs);
         step_set_dims(p, s, d, nd, -1);
         p->est_flops += 8.0 * (double)h;
-        buf_release(p, zbuf);
+        buf_release(p, z.buf);
     } else {
         /* odd length: full complex DFT of the real sequence, keep half */
-        i64 fts, lts[FA_MAXLOOPS], total;
-        int fbuf, nd;
-        fa_loc f;
-        fa_axis full_ax = ax, lay;
-        sdim d[FA_MAXLOOPS];
-        lay = ax;
-        lay.is = 1;
-        total = scratch_layout(&lay, nl, &fts, lts);
-        fbuf = buf_acquire(p, total);
-        f.buf = fbuf; f.base = 0; f.im = 1;
+        fa_axis full_ax = ax;
+        z = scratch_image(p, &ax, 1, nl, &zts, lts);
         full_ax.n = nl;
         full_ax.is = rs;
-        full_ax.os = fts;
+        full_ax.os = zts;
         full_ax.src = in;
-        full_ax.dst = f;
+        full_ax.dst = z;
         full_ax.flags_in = FFTW_AMD_F_REAL_IN;
         for (j = 0; j < ax.nloops; ++j) full_ax.loops[j].os = lts[j];
         fa_emit_axis(p, &full_ax);
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = lts[j]; d[nd].os = ax.loops[j].os;
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
-        emit_copy(p, FFTW_AMD_STEP_COPY, f, out, half, half, fts, cs, d, nd, 0, -1, -1);
-        buf_release(p, fbuf);
+        emit_copy(p, FFTW_AMD_STEP_COPY, z, out, half, half, zts, cs, d, loop_sdims(&ax, lts, NULL, d), 0, -1, -1);
+        buf_release(p, z.buf);
         return 0;
     }
     return epi != 0;
 }
 
+/* r2c: last dim real -> half spectrum, then complex DFTs over the other dims
+   on the half-spectrum array (reference rank_geq2_rdft2 A.c:10111-10282).
+   p->dims[].is are strides of the REAL array (doubles), .os of the complex
+   array (doubles, so 2 per complex). */
 static void build_r2c(plan *p) {
     int r = p->rank, a, j;
     i64 nl = p->dims[r - 1].n, half = nl / 2 + 1;
@@ -1909,16 +1870,6 @@ static void build_r2c(plan *p) {
     }
 }
 
-/* c2r: complex backward DFTs over the leading dims (into scratch, so the
-   caller's input survives), then half spectrum -> real along the last dim.
-   p->dims[].is: strides of the complex array, .os: of the real array. */
-/* half spectrum -> real along one axis (unnormalised backward).  ax: the loops
-   (.is = strides in the complex source `cur`, .os = strides in the real
-   destination); cs / rs: element strides of the transform index, in doubles. */
-/* pro: 0 = `cur` holds the half spectrum as complex numbers; FFTW_AMD_R2R_PRE_* =
-   `cur` is the user's real r2r input of stride cs and the tangle step applies
-   that prologue while loading (even lengths only, see r2r_can_fuse)
-   ps / pim: pair geometry of the real output, as in emit_r2c_axis */
 /* The backward twin of emit_r2c_decimated: a long c2r transform in TWO trips, n = L1 x L2 real points.
      trip 1   rows k1 = 0 ... L1 / 2 of the half spectrum read as [L2][L1]: Y[k2] = X[k1 + L1 k2] below L2 / 2, the
               conjugate of X[(L1 - k1) + L1 (L2 - 1 - k2)] above (every index stays within 0 ... n / 2), backward DFT
@@ -1939,116 +1890,68 @@ static void build_r2c(plan *p) {
    (no prologue / epilogue fusion here).  The plan never writes its input.  Reference counterpart: ct_hc2c backward
    (fftw/fftw_api.c:5551-5603, fftw/rdft_scalar/r2cb/hc2cbdft_*.c).  The first step has no fallback executor, so
    everything it needs is settled here.  1 = emitted. */
-static int emit_c2r_decimated(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, fa_loc out) {
-    fa_axis ax = *axp, c_ax, lay;
-    const i64 L2 = 2048;
-    i64 L1, h = nl / 2, zts, lts[FA_MAXLOOPS + 1], total;
-    int zbuf, j, nd, cloop, n0 = p->nsteps;
-    double flops0 = p->est_flops;
+static int emit_c2r_decimated(plan *p, i64 nl, const fa_axis *ax, fa_loc cur, fa_loc out) {
+    const i64 L2 = FA_DEC_L2, L1 = real_dec_geometry(p, nl, ax, cur, out, 0);
+    const int n0 = p->nsteps;
+    const double flops0 = p->est_flops;
+    i64 zts, lts[FA_MAXLOOPS + 1];
+    fa_axis c_ax;
     fa_loc z;
     sdim d[FA_MAXLOOPS + 1];
-    fftw_amd_step_desc *s;
-    if (!p->cfg.real_dec || p->type != FA_C2R || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_NARROW") ||
-        (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
-        return 0;
-    if (nl % L2 || !fa_hip_r3tw_cdec((int)L2) || fa_hip_r3t_tile((int)L2) < 8) return 0;
-    L1 = nl / L2;
-    if (L1 % 2 || L1 < 256) return 0;
-    /* trip 2 must be ONE strided pass: a register kernel of that length with 128-byte segments */
-    if (!((L1 <= 1024 && has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
-    if (ax.nloops >= FA_MAXLOOPS || cur.im != 1 || out.im != 0) return 0;
-    if ((cur.base % 2) || (out.base % 2) || (cur.buf < 2 && ((size_t)p->ri % 16)) || ((size_t)p->ro % 16)) return 0;
-    for (j = 0; j < ax.nloops; ++j)
-        if ((ax.loops[j].is % 2) || (ax.loops[j].os % 2)) return 0;
-
-    lay = ax;
-    lay.is = 1;
-    total = scratch_layout(&lay, h, &zts, lts);
-    zbuf = buf_acquire(p, total);
-    z.buf = zbuf; z.base = 0; z.im = 1;
-
-    nd = 0;
-    d[nd].n = L1 / 2 + 1; d[nd].is = 2; d[nd].os = (L2 / 2) * zts; d[nd].tw = 1; d[nd].is_batch = 0; ++nd;
-    for (j = 0; j < ax.nloops; ++j) {
-        d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = lts[j];
-        d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
+    int ok;
+    if (!L1) return 0;
+    z = scratch_image(p, ax, 1, nl / 2, &zts, lts);
+    d[0].n = L1 / 2 + 1; d[0].is = 2; d[0].os = (L2 / 2) * zts; d[0].tw = 1; d[0].is_batch = 0;
+    emit_pass(p, cur, z, L2, 2 * L1, zts, d, 1 + loop_sdims(ax, NULL, lts, d + 1), nl,
+              FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_DEC_C2R);
+    ok = !p->failed && real_dec_rows_step_ok(p, L1);
+    if (ok) {
+        c_ax = real_dec_column_axis(ax, L1, out, z, zts, lts, 0);
+        fa_emit_axis(p, &c_ax);
+        ok = !p->failed && p->nsteps == n0 + 2;
     }
-    emit_pass(p, cur, z, L2, 2 * L1, zts, d, nd, nl, FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_DEC_C2R);
-    if (p->failed) goto undo;
-    s = &p->steps[p->nsteps - 1];
-    if (s->variant != FFTW_AMD_K_R3 || s->tile != fa_hip_r3t_tile((int)L2) || s->tile_lo_n != 1 ||
-        s->dim_n[0] != L1 / 2 + 1 || s->dim_tw[0] != 1 || s->batch_dim == 0)
-        goto undo;
-
-    c_ax = ax;
-    cloop = c_ax.nloops++;
-    c_ax.loops[cloop].n = L2 / 2;
-    c_ax.loops[cloop].is = zts;
-    c_ax.loops[cloop].os = 2;
-    for (j = 0; j < ax.nloops; ++j) c_ax.loops[j].is = lts[j];
-    c_ax.n = L1;
-    c_ax.is = (L2 / 2) * zts;
-    c_ax.os = L2;                      /* L2 / 2 pairs of two doubles */
-    c_ax.src = z;
-    c_ax.dst = out;
-    c_ax.dst.im = 1;                   /* imaginary part = odd sample */
-    c_ax.dense = 0;
-    c_ax.flags_in = FFTW_AMD_F_SWAP_IN;
-    c_ax.flags_out = FFTW_AMD_F_SWAP_OUT;
-    fa_emit_axis(p, &c_ax);
-    if (p->failed || p->nsteps != n0 + 2) goto undo;
-    buf_release(p, zbuf);
-    return 1;
-undo:
-    if (p->failed) return 1;
-    p->nsteps = n0;
-    p->est_flops = flops0;
-    buf_release(p, zbuf);
-    return 0;
+    return real_dec_end(p, ok, n0, flops0, z.buf);
 }
 
+/* half spectrum -> real along one axis (unnormalised backward).  ax: the loops
+   (.is = strides in the complex source `cur`, .os = strides in the real
+   destination); cs / rs: element strides of the transform index, in doubles. */
+/* pro: 0 = `cur` holds the half spectrum as complex numbers; FFTW_AMD_R2R_PRE_* =
+   `cur` is the user's real r2r input of stride cs and the tangle step applies
+   that prologue while loading (even lengths only, see r2r_can_fuse)
+   ps / pim: pair geometry of the real output, as in emit_r2c_axis */
 static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 cs, fa_loc out, i64 rs, int pro,
                           i64 ps, i64 pim, int post) {
     fa_axis ax = *axp;
-    int j;
+    i64 zts, lts[FA_MAXLOOPS + 1];
+    sdim d[FA_MAXLOOPS + 1];
+    fftw_amd_step_desc *s;
+    fa_loc z;
+    int j, nd, rows_tile;
     if (ps == 0) { ps = 2 * rs; pim = rs; }
     if (pro == 0 && post == 0 && ps == 2 && pim == 1 && cs == 2 && emit_c2r_decimated(p, nl, &ax, cur, out)) return;
-    if (nl % 4 == 0 && nl >= 8 && ax.nloops < FA_MAXLOOPS && !getenv("FFTW_AMD_NO_RADIX4") &&
-        ((axis_pass_count(p, nl / 4) < half_axis_pass_count(p, nl / 2) && radix4_passes_have_kernels(p, nl / 4)) ||
-         getenv("FFTW_AMD_FORCE_RADIX4"))) {
+    if (use_radix4_real(p, nl, &ax)) {
         /* transpose of the radix-4 r2c plan: tangle into two quarter-length
            spectra, two backward complex DFTs of size m straight into the real array */
-        i64 m = nl / 4, zts, lts[FA_MAXLOOPS + 1], total;
-        int zbuf, nd, vloop;
-        fa_loc z;
+        i64 m = nl / 4;
         fa_axis q_ax = ax, lay;
-        sdim d[FA_MAXLOOPS + 1];
-        fftw_amd_step_desc *s;
-        vloop = q_ax.nloops++;
+        int vloop = q_ax.nloops++;
         q_ax.loops[vloop].n = 2;
         q_ax.loops[vloop].is = 0;
         q_ax.loops[vloop].os = ps;
         lay = q_ax;
-        lay.is = 2;
         lay.loops[vloop].is = 1;
-        total = scratch_layout(&lay, m, &zts, lts);
-        zbuf = buf_acquire(p, total);
-        z.buf = zbuf; z.base = 0; z.im = 1;
+        z = scratch_image(p, &lay, 2, m, &zts, lts);
         q_ax.dense = (pim == 1 && ps == 2);
 
         s = new_step(p, FFTW_AMD_STEP_C2R_PRE4);
-        s->src_buf = cur.buf; s->src_base = cur.base; s->src_im = cur.im;
-        s->dst_buf = zbuf; s->dst_base = 0; s->dst_im = 1;
+        step_set_locs(s, cur, z);
         s->is_l = cs;
         s->os_l = zts;
         s->aux_n = nl;
         s->aux_valid = lts[vloop];
         r2r_fuse_tables(p, s, nl, pro);
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = lts[j];
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
+        nd = loop_sdims(&ax, NULL, lts, d);
         s->kpos = order_dims_kpos(d, &nd, 0, cs);
         step_set_dims(p, s, d, nd, -1);
 
@@ -2062,68 +1965,27 @@ static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 c
         q_ax.flags_out = FFTW_AMD_F_SWAP_OUT;
         for (j = 0; j < q_ax.nloops; ++j) q_ax.loops[j].is = lts[j];
         fa_emit_axis(p, &q_ax);
-        buf_release(p, zbuf);
+        buf_release(p, z.buf);
     } else if (nl % 2 == 0 && nl >= 2 && (post != 0 || (ps == 2 && pim == 1)) &&
                (pro != 0 || (cs == 2 && cur.im == 1)) &&
-               (short_real_rows_tile(&ax, nl / 2, pro || post, 0) > 0 || real_rows_tile(nl / 2, pro || post) > 0) &&
-               c2r_rows_layout_ok(p, &ax, cur, out, pro, post)) {
-        /* contiguous rows of a supported length: tangle + backward half-length DFT in ONE trip */
-        sdim d[FA_MAXLOOPS];
-        int nd = 0;
-        fftw_amd_step_desc *s;
-        fa_loc dstp = out;
-        dstp.im = 1;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = ax.loops[j].os;
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
-        emit_pass(p, cur, dstp, nl / 2, pro ? cs : 2, post ? rs : 2, d, nd, 0, FFTW_AMD_F_C2R_ROWS);
-        s = &p->steps[p->nsteps - 1];
-        s->variant = FFTW_AMD_K_C2R;
-        s->aux_buf = post ? post : -1;   /* r2r output shuffle done by the kernel's store (FFTW_AMD_R2R_POST_E01 / O01) */
-        s->tile = short_real_rows_tile(&ax, nl / 2, pro || post, 0) > 0 ? short_real_rows_tile(&ax, nl / 2, pro || post, 0)
-                                                                        : real_rows_tile(nl / 2, pro || post);
-        s->tile_lo_n = 1;
-        s->aux_n = nl;              /* as in the r2c rows step: n, fused r2r prologue, twiddle multiplier */
-        s->aux_valid = pro;
-        if (pro == FFTW_AMD_R2R_PRE_E01 || pro == FFTW_AMD_R2R_PRE_O01) {
-            tab_tw2(p, 4 * nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-            s->aux_base = 4;
-        } else {
-            tab_tw2(p, nl, &s->tw_lo, &s->tw_hi, &s->tw_shift);
-            s->aux_base = 1;
-        }
-        p->est_flops += 8.0 * (double)(nl / 2);
+               (rows_tile = real_rows_tile_for(&ax, nl / 2, pro || post, 0)) > 0 &&
+               real_rows_layout_ok(p, &ax, cur, out, pro, post)) {
+        emit_real_rows_step(p, 0, nl, &ax, cur, cs, out, rs, pro, post, rows_tile);
     } else if (nl % 2 == 0 && nl >= 2) {
-        i64 h = nl / 2, zts, lts[FA_MAXLOOPS], total;
-        int zbuf, nd;
-        fa_loc z;
-        fa_axis half_ax, lay;
-        sdim d[FA_MAXLOOPS];
-        fftw_amd_step_desc *s;
-        lay = ax;
-        lay.is = 1;
-        total = scratch_layout(&lay, h, &zts, lts);
-        zbuf = buf_acquire(p, total);
-        z.buf = zbuf; z.base = 0; z.im = 1;
+        fa_axis half_ax = ax;
+        z = scratch_image(p, &ax, 1, nl / 2, &zts, lts);
 
         s = new_step(p, FFTW_AMD_STEP_C2R_PRE);
-        s->src_buf = cur.buf; s->src_base = cur.base; s->src_im = cur.im;
-        s->dst_buf = zbuf; s->dst_base = 0; s->dst_im = 1;
+        step_set_locs(s, cur, z);
         s->is_l = cs;
         s->os_l = zts;
         s->aux_n = nl;
         r2r_fuse_tables(p, s, nl, pro);
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = lts[j];
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
+        nd = loop_sdims(&ax, NULL, lts, d);
         s->kpos = order_dims_kpos(d, &nd, 0, cs);
         step_set_dims(p, s, d, nd, -1);
 
-        half_ax = ax;
-        half_ax.n = h;
+        half_ax.n = nl / 2;
         half_ax.is = zts;
         half_ax.os = ps;
         half_ax.src = z;
@@ -2133,29 +1995,15 @@ static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 c
         half_ax.flags_out = FFTW_AMD_F_SWAP_OUT;
         for (j = 0; j < ax.nloops; ++j) half_ax.loops[j].is = lts[j];
         fa_emit_axis(p, &half_ax);
-        buf_release(p, zbuf);
+        buf_release(p, z.buf);
     } else {
-        i64 fts, lts[FA_MAXLOOPS], total;
-        int fbuf, nd;
-        fa_loc f;
-        fa_axis full_ax, lay;
-        sdim d[FA_MAXLOOPS];
-        lay = ax;
-        lay.is = 1;
-        total = scratch_layout(&lay, nl, &fts, lts);
-        fbuf = buf_acquire(p, total);
-        f.buf = fbuf; f.base = 0; f.im = 1;
-        nd = 0;
-        for (j = 0; j < ax.nloops; ++j) {
-            d[nd].n = ax.loops[j].n; d[nd].is = ax.loops[j].is; d[nd].os = lts[j];
-            d[nd].tw = 0; d[nd].is_batch = (j == ax.batch_loop); ++nd;
-        }
-        emit_copy(p, FFTW_AMD_STEP_HERM_EXPAND, cur, f, nl, nl, cs, fts, d, nd, 0, -1, -1);
-        full_ax = ax;
+        fa_axis full_ax = ax;
+        z = scratch_image(p, &ax, 1, nl, &zts, lts);
+        emit_copy(p, FFTW_AMD_STEP_HERM_EXPAND, cur, z, nl, nl, cs, zts, d, loop_sdims(&ax, NULL, lts, d), 0, -1, -1);
         full_ax.n = nl;
-        full_ax.is = fts;
+        full_ax.is = zts;
         full_ax.os = rs;
-        full_ax.src = f;
+        full_ax.src = z;
         full_ax.dst = out;
         full_ax.flags_in = FFTW_AMD_F_SWAP_IN;
         /* backward by the swap identity: the real result is the imaginary
@@ -2163,10 +2011,13 @@ static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 c
         full_ax.flags_out = FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT;
         for (j = 0; j < ax.nloops; ++j) full_ax.loops[j].is = lts[j];
         fa_emit_axis(p, &full_ax);
-        buf_release(p, fbuf);
+        buf_release(p, z.buf);
     }
 }
 
+/* c2r: complex backward DFTs over the leading dims (into scratch, so the
+   caller's input survives), then half spectrum -> real along the last dim.
+   p->dims[].is: strides of the complex array, .os: of the real array. */
 static void build_c2r(plan *p) {
     int r = p->rank, a, j;
     i64 nl = p->dims[r - 1].n, half = nl / 2 + 1;
@@ -2255,24 +2106,15 @@ static fftw_amd_step_desc *emit_r2r_step(plan *p, int mode, i64 n, i64 K, i64 tw
                                          int order_by_dst) {
     fftw_amd_step_desc *s = new_step(p, FFTW_AMD_STEP_R2R);
     sdim d[FA_MAXLOOPS + 1];
-    int cnt = 0, i;
+    int cnt = loop_sdims(ax, lis, los, d);
     s->variant = mode;
-    s->src_buf = src.buf; s->src_base = src.base; s->src_im = src.im;
-    s->dst_buf = dst.buf; s->dst_base = dst.base; s->dst_im = dst.im;
+    step_set_locs(s, src, dst);
     s->is_l = is_k;
     s->os_l = os_k;
     s->aux_n = n;
     s->aux_valid = K;
     if (twmod) tab_tw2(p, twmod, &s->tw_lo, &s->tw_hi, &s->tw_shift);
     /* flatten order: smallest user-side stride fastest, the batch loop last */
-    for (i = 0; i < ax->nloops; ++i) {
-        d[cnt].n = ax->loops[i].n;
-        d[cnt].is = lis[i];
-        d[cnt].os = los[i];
-        d[cnt].tw = 0;
-        d[cnt].is_batch = (i == ax->batch_loop);
-        ++cnt;
-    }
     s->kpos = order_dims_kpos(d, &cnt, order_by_dst, order_by_dst ? os_k : is_k);
     step_set_dims(p, s, d, cnt, -1);
     p->est_flops += 4.0 * (double)K;
@@ -2351,13 +2193,13 @@ static void emit_r2r_axis(plan *p, int kind, i64 n, const fa_axis *axp, fa_loc i
        user's row itself -- the whole r2r axis is one trip */
     if (fuse_post && pre && pre != FFTW_AMD_R2R_PRE_HC2R && fa_hip_r2c_rows_tile((int)(N / 2)) > 0) {
         fa_axis tax = *axp;
-        if (r2c_rows_layout_ok(p, &tax, in, out, post, pre)) { rows_pre = pre; cntA = 0; }
+        if (real_rows_layout_ok(p, &tax, in, out, pre, post)) { rows_pre = pre; cntA = 0; }
     }
     if (inner == IN_C2R && pre && r2r_can_fuse(N)) { fuse_pre = 1; cntA = 0; }
     /* short rows: the fused c2r rows kernel also does the DCT-III / DST-III output shuffle */
     if (fuse_pre && post && fa_hip_r2c_rows_tile((int)(N / 2)) > 0) {
         fa_axis tax = *axp;
-        if (c2r_rows_layout_ok(p, &tax, in, out, pre, post)) { rows_post = post; cntB = 0; }
+        if (real_rows_layout_ok(p, &tax, in, out, pre, post)) { rows_post = post; cntB = 0; }
     }
 
     /* Real scratch sequences of even length are laid out as adjacent pairs

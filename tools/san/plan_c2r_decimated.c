@@ -1,5 +1,6 @@
 /*
- * plan_c2r_decimated.c -- host-only sanitizer check of the two-trip c2r planner path (emit_c2r_decimated).
+ * plan_c2r_decimated.c -- host-only sanitizer check of the two-trip c2r planner path (emit_c2r_decimated) and of the
+ * helpers it shares with its forward twin (emit_r2c_decimated, which the r2c problems below reach).
  * Plans c2r problems with FFTW_AMD_REAL_DEC=1 over the admissible and the inadmissible cases (no device is needed to
  * plan) with the C planner sources compiled under -fsanitize=address,undefined; `make san-c2r` builds and runs it.
  * The HIP units come from the ordinary library, only for the host-side tables (tile sizes, menus) the planner asks for.
@@ -47,6 +48,22 @@ static void c2r(const char *what, int rank, const int *n, int hm, unsigned flags
     fftw_free(y);
 }
 
+/* the forward twin: the decimated rows step is the LAST of its two steps */
+static void r2c(const char *what, int n, int hm, int want_dec) {
+    double *x = (double *)fftw_malloc(sizeof(double) * (size_t)hm * (size_t)n);
+    fftw_complex *y = (fftw_complex *)fftw_malloc(sizeof(fftw_complex) * (size_t)hm * (size_t)(n / 2 + 1));
+    fftw_plan p;
+    fftw_amd_step_desc d;
+    int steps, dec = 0;
+    if (!x || !y) { printf("out of memory\n"); exit(2); }
+    p = fftw_plan_many_dft_r2c(1, &n, hm, x, NULL, 1, n, y, NULL, 1, n / 2 + 1, FFTW_ESTIMATE);
+    steps = p ? fftw_amd_plan_num_steps(p) : -1;
+    if (steps > 0 && fftw_amd_plan_get_step(p, steps - 1, &d) == 0) dec = (d.flags & FFTW_AMD_F_REAL_DEC) != 0;
+    if (p) fftw_destroy_plan(p);
+    expect(what, steps, dec, want_dec);
+    fftw_free(x); fftw_free(y);
+}
+
 int main(void) {
     const int n1[1] = { 2048 * 256 }, n2[1] = { 2048 * 1000 }, n3[1] = { 1 << 22 }, bad[1] = { 2000 * 300 }, odd[1] = { 2048 * 255 };
     const int nd[2] = { 4, 2048 * 256 };
@@ -60,6 +77,10 @@ int main(void) {
     c2r("FFTW_UNALIGNED", 1, n1, 3, FFTW_ESTIMATE | FFTW_UNALIGNED, 0, 0);
     c2r("2000 x 300", 1, bad, 3, FFTW_ESTIMATE, 0, 0);
     c2r("2048 x 255 (odd L1)", 1, odd, 3, FFTW_ESTIMATE, 0, 0);
+    r2c("r2c 2048 x 256, batch 3", 2048 * 256, 3, 1);
+    r2c("r2c 2048 x 1024, batch 1", 2048 * 1024, 1, 1);
+    r2c("r2c 2048 x 2048, batch 1", 2048 * 2048, 1, 1);
+    r2c("r2c 2048 x 255 (odd L1)", 2048 * 255, 3, 0);
     {
         /* an r2r problem whose inner transform is a c2r keeps its plan */
         double *h = (double *)fftw_malloc(sizeof(double) * 3 * n1[0]), *z = (double *)fftw_malloc(sizeof(double) * 3 * n1[0]);
