@@ -9,7 +9,7 @@ LIBDIR := fftw3_amd/lib
 CFLAGS := -O2 -fPIC -std=gnu99 -Wall -Wextra -Iinclude -I$(CSRC)
 HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -std=c++17 -Wall
 
-OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o
+OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o
 
 all: $(LIBDIR)/libfftw3_amd.so
 
@@ -18,7 +18,11 @@ $(CSRC)/%.o: $(CSRC)/%.c $(CSRC)/fa_plan.h $(CSRC)/fa_hip.h $(CSRC)/split_costs.
 
 # every HIP unit depends on exactly the headers it includes (a full rebuild of the two menu units takes minutes)
 HIPCOMMON := $(CSRC)/common.hpp $(CSRC)/launch.hpp $(CSRC)/butterflies.h $(CSRC)/fa_hip.h include/fftw3_amd.h $(CSRC)/pass1024.hpp
-$(CSRC)/kernels.o: $(CSRC)/kernels.hip $(HIPCOMMON) $(CSRC)/r2r_epi.hpp
+$(CSRC)/kernels.o: $(CSRC)/kernels.hip $(HIPCOMMON)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/kernels_elem.o: $(CSRC)/kernels_elem.hip $(CSRC)/common.hpp $(CSRC)/launch.hpp $(CSRC)/butterflies.h $(CSRC)/fa_hip.h include/fftw3_amd.h $(CSRC)/r2r_epi.hpp
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/fa_hip.o: $(CSRC)/fa_hip.hip $(CSRC)/common.hpp $(CSRC)/butterflies.h $(CSRC)/fa_hip.h include/fftw3_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(CSRC)/kernels_rr.o: $(CSRC)/kernels_rr.hip $(HIPCOMMON) $(CSRC)/passrr.hpp $(CSRC)/pass3s.hpp $(CSRC)/pass3w.hpp $(CSRC)/rr_dispatch.hpp $(CSRC)/rr_menu.inc
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -221,6 +221,7 @@ _sig("fftw_amd_cexp", None, C.c_longlong, C.c_longlong, C.POINTER(C.c_double))
 _sig("fftw_amd_find_generator", C.c_longlong, C.c_longlong)
 _sig("fftw_amd_power_mod", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
 _sig("fftw_amd_factor_passes", C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong))
+_sig("fa_hip_elem_form", C.c_int, C.POINTER(StepDesc), C.c_int, C.c_int, C.c_longlong)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [_vp]
 
@@ -234,6 +235,18 @@ def p1024_launches():
     full, general = C.c_longlong(), C.c_longlong()
     lib.fftw_amd_p1024_launches(C.byref(full), C.byref(general))
     return full.value, general.value
+
+
+# enum fa_elem_form (csrc/fa_hip.h), in its order
+ELEM_FORMS = ("COPY_1", "COPY_4", "HERM", "POST2_DCT", "PRE2_DCT", "POST2_FAST", "PRE2_FAST", "POST2", "PRE2",
+              "POST4_FAST", "PRE4_FAST", "POST4", "PRE4", "R2R_SHUFFLE", "R2R_UNSHUFFLE", "R2R",
+              "RADER_MUL", "TRANSPOSE", "NONE")
+
+
+def elem_form(step, src_mis, dst_mis, cn):
+    """name of the kernel form that the element-wise step `step` takes for a chunk of cn transforms whose source /
+    destination addresses lie src_mis / dst_mis bytes past a 16-byte boundary ("NONE" for a pass); needs no device"""
+    return ELEM_FORMS[lib.fa_hip_elem_form(C.byref(step), src_mis, dst_mis, cn)]
 
 
 def ptr(x):

@@ -1,6 +1,7 @@
 /*
  * fa_hip.h -- the thin C ABI between the C host planner (api.c / planner.c)
- * and the HIP translation unit (kernels.hip).  Plain C types only.
+ * and the HIP translation units (runtime wrappers: fa_hip.hip, step dispatcher:
+ * kernels.hip).  Plain C types only.
  */
 #ifndef FA_HIP_H
 #define FA_HIP_H
@@ -26,6 +27,14 @@ int   fa_hip_r3_tile(int L);   /* rows per tile of the three-stage rows kernel f
 int   fa_hip_blue_nb(int need);  /* smallest padded length >= need of the one-kernel Bluestein, 0: none */
 int   fa_hip_blue_tile(int nb);  /* its rows per tile */
 int   fa_hip_r1_tile(int L);   /* rows per tile of the one-stage rows kernel (L = 2 ... 32), 0: none */
+/* The kernel form that an element-wise step takes (kernels_elem.hip) for a batch chunk of cn transforms whose
+   source / destination addresses are src_mis / dst_mis bytes past a 16-byte boundary.  Needs no device. */
+enum fa_elem_form {
+    FA_ELEM_COPY_1, FA_ELEM_COPY_4, FA_ELEM_HERM, FA_ELEM_POST2_DCT, FA_ELEM_PRE2_DCT, FA_ELEM_POST2_FAST, FA_ELEM_PRE2_FAST,
+    FA_ELEM_POST2, FA_ELEM_PRE2, FA_ELEM_POST4_FAST, FA_ELEM_PRE4_FAST, FA_ELEM_POST4, FA_ELEM_PRE4, FA_ELEM_R2R_SHUFFLE,
+    FA_ELEM_R2R_UNSHUFFLE, FA_ELEM_R2R, FA_ELEM_RADER_MUL, FA_ELEM_TRANSPOSE, FA_ELEM_NONE   /* NONE: not an element-wise step */
+};
+int   fa_hip_elem_form(const fftw_amd_step_desc *desc, int src_mis, int dst_mis, long long cn);
 void *fa_hip_malloc(size_t nbytes);
 void  fa_hip_free(void *p);
 void *fa_hip_host_malloc(size_t nbytes);  /* pinned; NULL when no device runtime */

@@ -1,6 +1,7 @@
 /*
  * launch.hpp -- host side shared by the launchers of the HIP units: the loop geometry of one step and batch chunk
- * (fa_step_geom), the launch of a kernel with dynamic LDS (fa_launch_lds) and the launchers' cross-unit prototypes.
+ * (fa_step_geom), the launch of a kernel with dynamic LDS (fa_launch_lds) and the launchers' cross-unit prototypes:
+ * the pass launchers, and fa_launch_copy / _real2 / _real4 / _r2r / _rader_mul of kernels_elem.hip (kernels.hip calls them).
  */
 #ifndef FA_LAUNCH_HPP
 #define FA_LAUNCH_HPP
@@ -132,6 +133,13 @@ int fa_launch_pass1r(const fftw_amd_step_desc *d, double *const *bufs, void *con
 int fa_launch_r2crows1(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
 /* kernels_sq.hip: FFTW_AMD_F_LO_DFT steps (rows + a DFT across the rows of a tile) */
 int fa_launch_lo_dft(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
+
+/* kernels_elem.hip: the element-wise steps, one launcher per step kind (0 = launched or nothing to do, -1 = error) */
+int fa_launch_copy(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);       /* COPY, HERM_EXPAND */
+int fa_launch_real2(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);      /* R2C_POST, C2R_PRE */
+int fa_launch_real4(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);      /* R2C_POST4, C2R_PRE4 */
+int fa_launch_r2r(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
+int fa_launch_rader_mul(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
 
 /* kernels_tr.hip: transposition steps (FFTW_AMD_STEP_COPY of variant FFTW_AMD_K_TRANSPOSE) */
 int fa_launch_transpose(const fftw_amd_step_desc *d, double *const *bufs, i64 cs, i64 cn, hipStream_t st);

@@ -11,7 +11,7 @@
  *   B   butterfly j -> (t, d), d fastest                    DFT-R2 over a -> c,  Z[d + R1 c]
  *   u   Z goes to two LDS planes [t][k]; then one item per Hermitian pair (k, L - k):
  *       Y[k] = E + w_n^k O,  Y[L-k] = conj(E - w_n^k O),  E = (Z[k] + conj Z[L-k]) / 2,
- *       O = -i (Z[k] - conj Z[L-k]) / 2     (r2c_post_kernel in kernels.hip)
+ *       O = -i (Z[k] - conj Z[L-k]) / 2     (r2c_post_kernel in kernels_elem.hip)
  * No predicates: out-of-range butterflies / rows redo the last valid one (pass3g.hpp).
  *
  * Reference counterpart: rdft2 plans whose child is a complex DFT over the (r0, r1) pairs

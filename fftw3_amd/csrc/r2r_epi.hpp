@@ -1,6 +1,6 @@
 /*
  * r2r_epi.hpp -- the r2r epilogue / prologue hooks shared by the untangle / tangle kernels
- * (kernels.hip) and the fused real-rows kernels (r2crows.hpp).  The argument struct A
+ * (kernels_elem.hip) and the fused real-rows kernels (r2crows.hpp).  The argument struct A
  * provides: dst / src, os_k / is_k, dst_im / src_im, flags, r2r (FFTW_AMD_R2R_* or 0),
  * rn (r2r length), tw_lo / tw_hi / tw_shift (modulus 4n for the 10 / 01 kinds).
  */

@@ -57,8 +57,10 @@ def environment(env):
 
 # ------------------------------------------------------------------ problems
 
-def real_many(fwd, n, hm=1, rstride=1, rdist=None, cstride=1, cdist=None, inplace=False, roff=0, coff=0, flags=fa.ESTIMATE):
-    """r2c (fwd) or c2r of the real shape n, howmany hm; strides / dists in elements of their own side"""
+def real_many(fwd, n, hm=1, rstride=1, rdist=None, cstride=1, cdist=None, inplace=False, roff=0, coff=0, flags=fa.ESTIMATE,
+              doubles=doubles):
+    """r2c (fwd) or c2r of the real shape n, howmany hm; strides / dists in elements of their own side;
+    doubles: the allocator (a GPU test passes one that returns device memory)"""
     n = list(n)
     total, half = int(np.prod(n)), int(np.prod(n[:-1])) * (n[-1] // 2 + 1)
     if inplace:                                  # FFTW's padded layout: rows of 2 (n / 2 + 1) doubles on both sides
@@ -88,7 +90,7 @@ def real_split(fwd, n, hm):
     return fa.plan_guru64_split_dft_c2r([(n, 1, 1)], [(hm, h, n)], re, im, r)
 
 
-def r2r_many(n, kinds, hm=1, inplace=False, off=0):
+def r2r_many(n, kinds, hm=1, inplace=False, off=0, doubles=doubles):
     n = list(n)
     total = int(np.prod(n))
     x = doubles(total * hm, off)
@@ -96,7 +98,7 @@ def r2r_many(n, kinds, hm=1, inplace=False, off=0):
     return fa.plan_many_r2r(len(n), n, hm, x, None, 1, total, y, None, 1, total, list(kinds))
 
 
-def c2c_many(n, hm=1, sign=fa.FORWARD, inplace=False):
+def c2c_many(n, hm=1, sign=fa.FORWARD, inplace=False, doubles=doubles):
     n = list(n)
     total = int(np.prod(n))
     x = doubles(2 * total * hm)
