@@ -56,12 +56,13 @@ F_SWAP_IN, F_SWAP_OUT, F_REAL_IN, F_REAL_OUT = 1, 2, 4, 8
 F_MUL_TABLE, F_MUL_CONJ, F_PERM_SRC, F_PERM_DST, F_CONJ_OUT, F_TW_IN = 16, 32, 64, 128, 256, 512
 F_R2C_ROWS = 1024
 F_C2R_ROWS = 2048
+F_NT_IN, F_NT_OUT = 1 << 12, 1 << 13
 F_LO_DFT = 1 << 14
 F_REAL_DEC = 1 << 15
 F_REAL_DEC_C2R = 1 << 17
 F_PAIR_SWAP = 1 << 16
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
-K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE = range(9)
+K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D = range(10)
 
 
 class StepDesc(C.Structure):

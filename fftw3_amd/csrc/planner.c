@@ -1334,6 +1334,49 @@ static int emit_rows_lo_dft(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_ou
     return 1;
 }
 
+/* A batch of small two-dimensional transforms n0 x n1 (both extents at most 32, a pair of img2d_menu.inc) on dense
+   contiguous images, in ONE trip: a workgroup takes T whole images and does both axes in registers
+   (FFTW_AMD_K_IMG2D, pass2d.hpp), where the axis-by-axis plan crosses HBM twice.  The step has no other executor, so
+   everything it needs is settled here: rank 2, interleaved arrays, dense rows and images, at most one howmany loop
+   (mk_guru drops the extent-1 ones) that steps over exactly one image on both sides, 16-byte aligned arrays, no
+   FFTW_UNALIGNED.  No scratch, in place or out of place.  fa_hip_img2d_tile is the only source of what the kernel
+   covers.  FFTW_AMD_NO_IMG2D=1 restores the two-trip plans.  1 = emitted. */
+static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    const fa_dim *col = &p->dims[0], *row = &p->dims[1];
+    fftw_amd_step_desc *s;
+    sdim d;
+    i64 n0, n1, img;
+    int T;
+    if (p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    n0 = col->n; n1 = row->n;
+    if (n0 > 32 || n1 > 32) return 0;
+    T = fa_hip_img2d_tile((int)n0, (int)n1);
+    if (T <= 0) return 0;
+    img = 2 * n0 * n1;
+    if (in.im != 1 || out.im != 1) return 0;
+    if (row->is != 2 || row->os != 2 || col->is != 2 * n1 || col->os != 2 * n1) return 0;
+    if (p->hrank && (p->hdims[0].is != img || p->hdims[0].os != img)) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    s = new_step(p, FFTW_AMD_STEP_PASS);
+    step_set_locs(s, in, out);
+    s->flags = sw_in | sw_out | FFTW_AMD_F_LO_DFT;
+    s->L = (int)n1;
+    s->is_l = 2;
+    s->os_l = 2;
+    s->nradices = fa_radices(n1, s->radices);
+    if (s->nradices < 0) { p->failed = 1; return 1; }
+    s->tile_lo_n = (int)n0;
+    s->tile_lo_is = 2 * n1;
+    s->tile_lo_os = 2 * n1;
+    d.n = p->hrank ? p->chunk : 1; d.is = img; d.os = img; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
+    step_set_dims(p, s, &d, 1, 0);
+    s->tile = T;
+    s->variant = FFTW_AMD_K_IMG2D;
+    p->est_flops += 5.0 * (double)(n0 * n1) * (double)d.n * log2((double)(n0 * n1));
+    return 1;
+}
+
 static void build_c2c_on(plan *p, fa_loc in, fa_loc out);
 
 /* One copy src -> dst over ALL dims of the problem as loops (transform dims, then the howmany dims of the current
@@ -1443,6 +1486,7 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
         return;
     }
     if (emit_rows_lo_dft(p, in, out, sw_in, sw_out)) return;
+    if (emit_img2d(p, in, out, sw_in, sw_out)) return;
     for (a = p->rank - 1; a >= 0; --a) {
         fa_axis ax;
         memset(&ax, 0, sizeof(ax));
@@ -2932,6 +2976,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_R3 && (d->flags & FFTW_AMD_F_REAL_DEC_C2R)) sapp(s, cap, &len, "reg3+c2r-decimated");
             else if (d->variant == FFTW_AMD_K_R3) sapp(s, cap, &len, (d->flags & FFTW_AMD_F_LO_DFT) ? (d->tile_lo_n == 4 ? "reg3+dft4-across-rows" : "reg3+dft2-across-rows") : "reg3");
             else if (d->variant == FFTW_AMD_K_R1) sapp(s, cap, &len, "reg1");
+            else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);
             else {
                 sapp(s, cap, &len, "lds:");

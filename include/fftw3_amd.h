@@ -332,11 +332,16 @@ enum {
     FFTW_AMD_K_R1 = 6,          /* one-stage register kernel: dense rows of 2 ... 32 points, one butterfly per row */
     FFTW_AMD_K_BLUE = 7,        /* Bluestein's algorithm for a whole row in one kernel (pass3b.hpp): L = padded length nb,
                                    aux_n = n, tw_lo / tw_hi = ids of the chirp and the kernel table */
-    FFTW_AMD_K_TRANSPOSE = 8    /* FFTW_AMD_STEP_COPY that is a batched transposition of n0 x n1 matrices of tuples, through
+    FFTW_AMD_K_TRANSPOSE = 8,   /* FFTW_AMD_STEP_COPY that is a batched transposition of n0 x n1 matrices of tuples, through
                                    LDS tiles (transpose.hpp): dims[0] = (n0, source leading dimension, vl), dims[1] =
                                    (n1, vl, destination leading dimension), dims[2 ...] the outer batch loops, the tuple of
                                    vl doubles as the copy's own index (aux_n elements at is_l = os_l).  Every field keeps
                                    the meaning it has for any other copy */
+    FFTW_AMD_K_IMG2D = 9        /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT: whole small images in one trip (pass2d.hpp).  The
+                                   step is the 2-D DFT tile_lo_n x L of dense row-major images: L = n1 columns (is_l = os_l = 2),
+                                   tile_lo_n = n0 rows (tile_lo_is = tile_lo_os = 2 n1), dims[0] the loop over the images of the
+                                   chunk (strides 2 n0 n1), tile = images per workgroup, no twiddle, no tables.  No fallback
+                                   executor: planned only for aligned interleaved arrays */
 };
 
 enum {
