@@ -62,7 +62,7 @@ F_REAL_DEC = 1 << 15
 F_REAL_DEC_C2R = 1 << 17
 F_PAIR_SWAP = 1 << 16
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
-K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D = range(10)
+K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL = range(11)
 
 
 class StepDesc(C.Structure):
@@ -223,6 +223,7 @@ _sig("fftw_amd_find_generator", C.c_longlong, C.c_longlong)
 _sig("fftw_amd_power_mod", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong)
 _sig("fftw_amd_factor_passes", C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong))
 _sig("fa_hip_elem_form", C.c_int, C.POINTER(StepDesc), C.c_int, C.c_int, C.c_longlong)
+_sig("fa_hip_img2dl_tile", C.c_int, C.c_int, C.c_int)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [_vp]
 
@@ -242,6 +243,12 @@ def p1024_launches():
 ELEM_FORMS = ("COPY_1", "COPY_4", "HERM", "POST2_DCT", "PRE2_DCT", "POST2_FAST", "PRE2_FAST", "POST2", "PRE2",
               "POST4_FAST", "PRE4_FAST", "POST4", "PRE4", "R2R_SHUFFLE", "R2R_UNSHUFFLE", "R2R",
               "RADER_MUL", "TRANSPOSE", "NONE")
+
+
+def img2dl_tile(n0, n1):
+    """images per workgroup of the one-trip image kernel for extents above 32 (pass2dl.hpp, img2dl_menu.inc) for images
+    of n0 rows x n1 columns; 0: the kernel does not cover that size.  Needs no device"""
+    return int(lib.fa_hip_img2dl_tile(n0, n1))
 
 
 def elem_form(step, src_mis, dst_mis, cn):

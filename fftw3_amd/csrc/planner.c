@@ -1334,14 +1334,18 @@ static int emit_rows_lo_dft(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_ou
     return 1;
 }
 
-/* A batch of small two-dimensional transforms n0 x n1 (both extents at most 32, a pair of img2d_menu.inc) on dense
-   contiguous images, in ONE trip: a workgroup takes T whole images and does both axes in registers
-   (FFTW_AMD_K_IMG2D, pass2d.hpp), where the axis-by-axis plan crosses HBM twice.  The step has no other executor, so
-   everything it needs is settled here: rank 2, interleaved arrays, dense rows and images, at most one howmany loop
-   (mk_guru drops the extent-1 ones) that steps over exactly one image on both sides, 16-byte aligned arrays, no
-   FFTW_UNALIGNED.  No scratch, in place or out of place.  fa_hip_img2d_tile is the only source of what the kernel
-   covers.  FFTW_AMD_NO_IMG2D=1 restores the two-trip plans.  1 = emitted. */
-static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+/* A batch of small two-dimensional transforms n0 x n1 on dense contiguous images, in ONE trip: a workgroup takes T
+   whole images and does both axes in registers, where the axis-by-axis plan crosses HBM twice.  Two kernel families:
+   both extents at most 32, a pair of img2d_menu.inc, one butterfly per axis (FFTW_AMD_K_IMG2D, pass2d.hpp); extents in
+   {16, 32, 40, 48, 64} with at least one above 32, a pair of img2dl_menu.inc, two register stages on an axis of 40, 48
+   or 64 points (FFTW_AMD_K_IMG2DL, pass2dl.hpp), whose intra-axis twiddles w_n^(a d) come from the stage tables of the
+   axes: table (row axis) and table2 (column axis), which no executor of a pass without tw_n reads otherwise.  The
+   steps have no other executor, so everything they need is settled here: rank 2, interleaved arrays, dense rows and
+   images, at most one howmany loop (mk_guru drops the extent-1 ones) that steps over exactly one image on both sides,
+   16-byte aligned arrays, no FFTW_UNALIGNED.  No scratch, in place or out of place.  fa_hip_img2d_tile and
+   fa_hip_img2dl_tile are the only sources of what the kernels cover.  FFTW_AMD_NO_IMG2D=1 (no whole images in one
+   trip) restores the two-trip plans for both.  1 = emitted. */
+static int emit_images(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, int variant) {
     const fa_dim *col = &p->dims[0], *row = &p->dims[1];
     fftw_amd_step_desc *s;
     sdim d;
@@ -1349,8 +1353,8 @@ static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     int T;
     if (p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
     n0 = col->n; n1 = row->n;
-    if (n0 > 32 || n1 > 32) return 0;
-    T = fa_hip_img2d_tile((int)n0, (int)n1);
+    if (n0 > 64 || n1 > 64) return 0;
+    T = (variant == FFTW_AMD_K_IMG2D) ? fa_hip_img2d_tile((int)n0, (int)n1) : fa_hip_img2dl_tile((int)n0, (int)n1);
     if (T <= 0) return 0;
     img = 2 * n0 * n1;
     if (in.im != 1 || out.im != 1) return 0;
@@ -1372,9 +1376,21 @@ static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     d.n = p->hrank ? p->chunk : 1; d.is = img; d.os = img; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
     step_set_dims(p, s, &d, 1, 0);
     s->tile = T;
-    s->variant = FFTW_AMD_K_IMG2D;
+    s->variant = variant;
+    if (variant == FFTW_AMD_K_IMG2DL) {
+        if (n1 > 32) s->table = tab_stage(p, n1);
+        if (n0 > 32) s->table2 = tab_stage(p, n0);
+    }
     p->est_flops += 5.0 * (double)(n0 * n1) * (double)d.n * log2((double)(n0 * n1));
     return 1;
+}
+
+static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    return emit_images(p, in, out, sw_in, sw_out, FFTW_AMD_K_IMG2D);
+}
+
+static int emit_img2dl(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    return emit_images(p, in, out, sw_in, sw_out, FFTW_AMD_K_IMG2DL);
 }
 
 static void build_c2c_on(plan *p, fa_loc in, fa_loc out);
@@ -1487,6 +1503,7 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
     }
     if (emit_rows_lo_dft(p, in, out, sw_in, sw_out)) return;
     if (emit_img2d(p, in, out, sw_in, sw_out)) return;
+    if (emit_img2dl(p, in, out, sw_in, sw_out)) return;
     for (a = p->rank - 1; a >= 0; --a) {
         fa_axis ax;
         memset(&ax, 0, sizeof(ax));
@@ -2977,6 +2994,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_R3) sapp(s, cap, &len, (d->flags & FFTW_AMD_F_LO_DFT) ? (d->tile_lo_n == 4 ? "reg3+dft4-across-rows" : "reg3+dft2-across-rows") : "reg3");
             else if (d->variant == FFTW_AMD_K_R1) sapp(s, cap, &len, "reg1");
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);
             else {
                 sapp(s, cap, &len, "lds:");

@@ -337,11 +337,16 @@ enum {
                                    (n1, vl, destination leading dimension), dims[2 ...] the outer batch loops, the tuple of
                                    vl doubles as the copy's own index (aux_n elements at is_l = os_l).  Every field keeps
                                    the meaning it has for any other copy */
-    FFTW_AMD_K_IMG2D = 9        /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT: whole small images in one trip (pass2d.hpp).  The
+    FFTW_AMD_K_IMG2D = 9,       /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT: whole small images in one trip (pass2d.hpp).  The
                                    step is the 2-D DFT tile_lo_n x L of dense row-major images: L = n1 columns (is_l = os_l = 2),
                                    tile_lo_n = n0 rows (tile_lo_is = tile_lo_os = 2 n1), dims[0] the loop over the images of the
                                    chunk (strides 2 n0 n1), tile = images per workgroup, no twiddle, no tables.  No fallback
                                    executor: planned only for aligned interleaved arrays */
+    FFTW_AMD_K_IMG2DL = 10      /* the same step (every field as for FFTW_AMD_K_IMG2D) for extents in {16, 32, 40, 48, 64} with at
+                                   least one above 32 (pass2dl.hpp): an axis of 40, 48 or 64 points is two register stages, whose
+                                   intra-axis twiddles are the stage tables `table` (row axis, L entries) and `table2` (column
+                                   axis, tile_lo_n entries), -1 for an axis of one stage; tw_n = 0.  The plan owns these tables, so
+                                   fftw_amd_plan_workspace_bytes is 16 bytes per entry of them; it owns no scratch buffer */
 };
 
 enum {
