@@ -60,9 +60,10 @@ F_NT_IN, F_NT_OUT = 1 << 12, 1 << 13
 F_LO_DFT = 1 << 14
 F_REAL_DEC = 1 << 15
 F_REAL_DEC_C2R = 1 << 17
+F_REAL_IMG = 1 << 18
 F_PAIR_SWAP = 1 << 16
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
-K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL = range(11)
+K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL, K_IMG2DR = range(12)
 
 
 class StepDesc(C.Structure):
@@ -224,6 +225,7 @@ _sig("fftw_amd_power_mod", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlon
 _sig("fftw_amd_factor_passes", C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong))
 _sig("fa_hip_elem_form", C.c_int, C.POINTER(StepDesc), C.c_int, C.c_int, C.c_longlong)
 _sig("fa_hip_img2dl_tile", C.c_int, C.c_int, C.c_int)
+_sig("fa_hip_img2dr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [_vp]
 
@@ -249,6 +251,12 @@ def img2dl_tile(n0, n1):
     """images per workgroup of the one-trip image kernel for extents above 32 (pass2dl.hpp, img2dl_menu.inc) for images
     of n0 rows x n1 columns; 0: the kernel does not cover that size.  Needs no device"""
     return int(lib.fa_hip_img2dl_tile(n0, n1))
+
+
+def img2dr_tile(n0, n1, fwd=True):
+    """images per workgroup of the one-trip real-image kernels (pass2dr.hpp, img2dr_menu.inc) for images of n0 rows x
+    n1 real columns, r2c (fwd) or c2r; 0: the kernels do not cover that size.  Needs no device"""
+    return int(lib.fa_hip_img2dr_tile(n0, n1, 1 if fwd else 0))
 
 
 def elem_form(step, src_mis, dst_mis, cn):

@@ -68,6 +68,9 @@ typedef struct {
     int real_dec;         /* FFTW_AMD_REAL_DEC: long r2c transforms decimated over the real data (two trips on the 512-item
                              kernels, emit_r2c_decimated) instead of the half- / quarter-length plans; off by default
                              (measured a few % behind them except near n = 2^20), a FFTW_MEASURE candidate */
+    int real_img;         /* FFTW_AMD_REAL_IMG: batches of small 2-D r2c / c2r transforms in one trip (emit_real_image,
+                             FFTW_AMD_K_IMG2DR) instead of the three-trip plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
+                             candidate */
 } fa_cfg;
 
 typedef struct {

@@ -54,6 +54,7 @@ fa_cfg fa_default_cfg(void) {
     c.long_first = 0;
     c.tile_elems = 0;
     c.real_dec = 0;
+    c.real_img = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -69,6 +70,8 @@ fa_cfg fa_default_cfg(void) {
     if (e && atoll(e) >= 16) c.lmax_multi = (int)atoll(e);
     e = getenv("FFTW_AMD_REAL_DEC");
     if (e) c.real_dec = atoi(e) != 0;
+    e = getenv("FFTW_AMD_REAL_IMG");
+    if (e) c.real_img = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
@@ -1902,6 +1905,57 @@ static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs,
     return epi != 0;
 }
 
+/* A batch of small two-dimensional r2c (fwd) or c2r transforms n0 x n1 in ONE trip (FFTW_AMD_K_IMG2DR, pass2dr.hpp): a
+   workgroup takes T whole real images and does both axes in registers, where the axis-by-axis plans make three trips
+   (a pass, the untangle / tangle, a pass), two of them on the runtime-radix LDS kernel, through a scratch buffer.  The
+   step has no other executor, so everything it needs is settled here: rank 2, at most one howmany loop that steps over
+   exactly one image on both sides, the real side with element stride 1 and row pitch n1 or n1 + 2, the complex side
+   interleaved with stride 2 and row pitch n1 + 2, 16-byte aligned arrays, no FFTW_UNALIGNED.  No scratch, no table;
+   in place with padded rows (an image then occupies the same words on both sides).  fa_hip_img2dr_tile is the only
+   source of what the kernels cover.  Off under FFTW_ESTIMATE (cfg.real_img, FFTW_AMD_REAL_IMG=1): the numpy
+   interpreter of the test suite's existing files does not know the step, and those files plan such problems with
+   default settings; a candidate of the FFTW_MEASURE search for r2c / c2r problems, remembered by wisdom.
+   FFTW_AMD_NO_IMG2D=1 and FFTW_AMD_NO_TUNED=1 switch it off like the complex image steps.  1 = emitted. */
+static int emit_real_image(plan *p, int fwd) {
+    const fa_dim *col = &p->dims[0], *row = &p->dims[1];
+    fftw_amd_step_desc *s;
+    fa_loc in = { 0, 0, fwd ? 0 : p->in_im }, out = { 1, 0, fwd ? p->out_im : 0 };
+    sdim d;
+    i64 n0, n1, cp, rp, r_el, c_el, c_row, r_img, c_img;
+    int T;
+    if (!p->cfg.real_img || p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    n0 = col->n; n1 = row->n;
+    if (n0 > 32 || n1 > 32) return 0;
+    T = fa_hip_img2dr_tile((int)n0, (int)n1, fwd);
+    if (T <= 0) return 0;
+    cp = n1 + 2;
+    r_el = fwd ? row->is : row->os; c_el = fwd ? row->os : row->is;
+    rp = fwd ? col->is : col->os; c_row = fwd ? col->os : col->is;
+    if ((fwd ? p->out_im : p->in_im) != 1) return 0;
+    if (r_el != 1 || c_el != 2 || c_row != cp || (rp != n1 && rp != cp)) return 0;
+    r_img = n0 * rp; c_img = n0 * cp;
+    if (p->hrank && ((fwd ? p->hdims[0].is : p->hdims[0].os) != r_img || (fwd ? p->hdims[0].os : p->hdims[0].is) != c_img)) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    s = new_step(p, FFTW_AMD_STEP_PASS);
+    step_set_locs(s, in, out);
+    s->flags = FFTW_AMD_F_REAL_IMG | (fwd ? FFTW_AMD_F_REAL_IN : FFTW_AMD_F_REAL_OUT);
+    s->L = (int)n1;
+    s->is_l = fwd ? 1 : 2;
+    s->os_l = fwd ? 2 : 1;
+    s->nradices = fa_radices(n1, s->radices);
+    if (s->nradices < 0) { p->failed = 1; return 1; }
+    s->tile_lo_n = (int)n0;
+    s->tile_lo_is = fwd ? rp : cp;
+    s->tile_lo_os = fwd ? cp : rp;
+    d.n = p->hrank ? p->chunk : 1; d.is = fwd ? r_img : c_img; d.os = fwd ? c_img : r_img; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
+    step_set_dims(p, s, &d, 1, 0);
+    s->tile = T;
+    s->variant = FFTW_AMD_K_IMG2DR;
+    p->est_flops += 2.5 * (double)(n0 * n1) * (double)d.n * log2((double)(n0 * n1));
+    return 1;
+}
+
 /* r2c: last dim real -> half spectrum, then complex DFTs over the other dims
    on the half-spectrum array (reference rank_geq2_rdft2 A.c:10111-10282).
    p->dims[].is are strides of the REAL array (doubles), .os of the complex
@@ -1912,6 +1966,7 @@ static void build_r2c(plan *p) {
     i64 ext[FA_MAXRANK];
     fa_loc in = { 0, 0, 0 }, out = { 1, 0, p->out_im };
     fa_axis ax;
+    if (emit_real_image(p, 1)) return;
     for (j = 0; j < r; ++j) ext[j] = p->dims[j].n;
     ext[r - 1] = half;
 
@@ -2090,6 +2145,7 @@ static void build_c2r(plan *p) {
     int cbuf = -1;
     fa_axis ax;
 
+    if (emit_real_image(p, 0)) return;
     for (j = 0; j < r; ++j) { ext[j] = p->dims[j].n; cdims[j] = p->dims[j]; cdims[j].os = p->dims[j].is; }
     ext[r - 1] = half;
     for (j = 0; j < p->hrank; ++j) { chd[j] = p->hdims[j]; chd[j].os = p->hdims[j].is; }
@@ -2995,6 +3051,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_R1) sapp(s, cap, &len, "reg1");
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_IMG2DR) sapp(s, cap, &len, "img2d-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);
             else {
                 sapp(s, cap, &len, "lds:");

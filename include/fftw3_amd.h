@@ -342,11 +342,13 @@ enum {
                                    tile_lo_n = n0 rows (tile_lo_is = tile_lo_os = 2 n1), dims[0] the loop over the images of the
                                    chunk (strides 2 n0 n1), tile = images per workgroup, no twiddle, no tables.  No fallback
                                    executor: planned only for aligned interleaved arrays */
-    FFTW_AMD_K_IMG2DL = 10      /* the same step (every field as for FFTW_AMD_K_IMG2D) for extents in {16, 32, 40, 48, 64} with at
+    FFTW_AMD_K_IMG2DL = 10,     /* the same step (every field as for FFTW_AMD_K_IMG2D) for extents in {16, 32, 40, 48, 64} with at
                                    least one above 32 (pass2dl.hpp): an axis of 40, 48 or 64 points is two register stages, whose
                                    intra-axis twiddles are the stage tables `table` (row axis, L entries) and `table2` (column
                                    axis, tile_lo_n entries), -1 for an axis of one stage; tw_n = 0.  The plan owns these tables, so
                                    fftw_amd_plan_workspace_bytes is 16 bytes per entry of them; it owns no scratch buffer */
+    FFTW_AMD_K_IMG2DR = 11      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole small REAL images in one trip, r2c or c2r
+                                   (pass2dr.hpp); see the flag for the fields.  No fallback executor */
 };
 
 enum {
@@ -382,6 +384,23 @@ enum {
                                       destination are the same array, equal leading dimensions): workgroups exchange the tile
                                       pairs (ti, tj) / (tj, ti) in place, no scratch.  As for every copy, all reads happen
                                       before any write of the same word */
+    FFTW_AMD_F_REAL_IMG  = 1 << 18,/* pass of variant FFTW_AMD_K_IMG2DR: the whole 2-D r2c (with FFTW_AMD_F_REAL_IN) or c2r (with
+                                      FFTW_AMD_F_REAL_OUT) transform of real images of tile_lo_n = n0 rows x L = n1 real columns,
+                                      n1 even, both at most 32.  dims[0] is the loop over the images of the chunk, tile = images
+                                      per workgroup, tw_n = 0, table = table2 = -1, no swap flags.  The complex side is the
+                                      dense half spectrum: n0 rows of n1 / 2 + 1 interleaved entries (im = 1, entries 2 apart,
+                                      rows n1 + 2 doubles apart, images n0 (n1 + 2) apart); the real side has im = 0, elements 1
+                                      apart, rows `pitch` = n1 or n1 + 2 doubles apart and images n0 pitch apart.
+                                      r2c: src_im = 0, is_l = 1, tile_lo_is = pitch, dim_is[0] = n0 pitch; dst_im = 1, os_l = 2,
+                                      tile_lo_os = n1 + 2, dim_os[0] = n0 (n1 + 2);
+                                      Y[k0][k1] = sum x[j0][j1] w_n0^(j0 k0) w_n1^(j1 k1) for k1 = 0 ... n1 / 2.
+                                      c2r: the same fields with the sides exchanged (src_im = 1, is_l = 2, tile_lo_is = n1 + 2,
+                                      dst_im = 0, os_l = 1, tile_lo_os = pitch).  First the backward DFT of length n0 down each
+                                      of the n1 / 2 + 1 columns, then the 1-D c2r of length n1 along each row, which reads the
+                                      imaginary parts of its entries 0 and n1 / 2 as 0 (half spectra need not be Hermitian).
+                                      With pitch = n1 + 2 an image occupies the same words on both sides and the step may run
+                                      in place: every word of an image is read before any is written.  The padding words of
+                                      padded real rows are never written.  Planned only for aligned arrays */
     FFTW_AMD_F_REAL_DEC_C2R = 1 << 17 /* pass: the FIRST trip of a two-trip c2r transform of n = L1 x L real points (pass3t_kernel,
                                       RD = 2), the backward twin of FFTW_AMD_F_REAL_DEC.  The source is the half spectrum
                                       X[0 ... n / 2], entry k at k1 dim_is[0] + k2 is_l for k = k1 + L1 k2 (so is_l = L1 dim_is[0]).
