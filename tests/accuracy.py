@@ -188,53 +188,62 @@ def _cs(num, den, fn):
 def ld_r2r(x, kind):
     """the eleven r2r kinds by their defining sums (FFTW manual, "What FFTW Really Computes"), long double,
     unnormalised, for n <= 4096.  kind = FFTW's enum: R2HC 0, HC2R 1, DHT 2, REDFT00 3, REDFT01 4, REDFT10 5,
-    REDFT11 6, RODFT00 7, RODFT01 8, RODFT10 9, RODFT11 10.  x: (n,) or (howmany, n)."""
+    REDFT11 6, RODFT00 7, RODFT01 8, RODFT10 9, RODFT11 10.  x: (n,) or (howmany, n); the rows of a batch share
+    each block of the cosine / sine matrix, and every row is summed as it would be alone."""
     _check()
     x = np.asarray(x, dtype=LD)
-    if x.ndim == 2:
-        return np.stack([ld_r2r(r, kind) for r in x])
-    n = x.shape[0]
+    if x.ndim == 1:
+        return ld_r2r(x[None, :], kind)[0]
+    n = x.shape[1]
     assert n <= 4096
     j = np.arange(n, dtype=np.int64)[None, :]
-    out = np.empty(n, dtype=LD)
+    out = np.empty(x.shape, dtype=LD)
     blk = max(1, (1 << 20) // n)
     for k0 in range(0, n, blk):
         k = np.arange(k0, min(n, k0 + blk), dtype=np.int64)[:, None]
         sgn = np.where(k[:, 0] % 2 == 0, LD(1), LD(-1))
         if kind == 0:          # R2HC: r0 ... r(n/2), i((n+1)/2 - 1) ... i1
             q = np.where(k <= n // 2, k, n - k)
-            re = np.sum(x * _cs(2 * j * q, n, np.cos), axis=1)
-            im = -np.sum(x * _cs(2 * j * q, n, np.sin), axis=1)
-            v = np.where(k[:, 0] <= n // 2, re, im)
+            c, s, low = _cs(2 * j * q, n, np.cos), _cs(2 * j * q, n, np.sin), k[:, 0] <= n // 2
+            f = lambda r: np.where(low, np.sum(r * c, axis=1), -np.sum(r * s, axis=1))
         elif kind == 1:        # HC2R: x0 + 2 sum (r_q cos - i_q sin) (+ r(n/2) (-1)^k for even n)
             q = np.arange(1, (n + 1) // 2, dtype=np.int64)[None, :]
-            v = x[0] + 2 * np.sum(x[1:(n + 1) // 2] * _cs(2 * q * k, n, np.cos)
-                                  - x[n - q[0]] * _cs(2 * q * k, n, np.sin), axis=1)
+            c, s = _cs(2 * q * k, n, np.cos), _cs(2 * q * k, n, np.sin)
             if n % 2 == 0:
-                v = v + sgn * x[n // 2]
+                f = lambda r: r[0] + 2 * np.sum(r[1:(n + 1) // 2] * c - r[n - q[0]] * s, axis=1) + sgn * r[n // 2]
+            else:
+                f = lambda r: r[0] + 2 * np.sum(r[1:(n + 1) // 2] * c - r[n - q[0]] * s, axis=1)
         elif kind == 2:        # DHT
-            v = np.sum(x * (_cs(2 * j * k, n, np.cos) + _cs(2 * j * k, n, np.sin)), axis=1)
+            c = _cs(2 * j * k, n, np.cos) + _cs(2 * j * k, n, np.sin)
+            f = lambda r: np.sum(r * c, axis=1)
         elif kind == 3:        # REDFT00, logical N = 2(n - 1)
-            v = x[0] + sgn * x[n - 1]
             if n > 2:
-                v = v + 2 * np.sum(x[1:n - 1] * _cs(j[:, 1:n - 1] * k, n - 1, np.cos), axis=1)
+                c = _cs(j[:, 1:n - 1] * k, n - 1, np.cos)
+                f = lambda r: r[0] + sgn * r[n - 1] + 2 * np.sum(r[1:n - 1] * c, axis=1)
+            else:
+                f = lambda r: r[0] + sgn * r[n - 1]
         elif kind == 4:        # REDFT01
-            v = x[0] + 2 * np.sum(x[1:] * _cs(j[:, 1:] * (2 * k + 1), 2 * n, np.cos), axis=1)
-        elif kind == 5:        # REDFT10
-            v = 2 * np.sum(x * _cs((2 * j + 1) * k, 2 * n, np.cos), axis=1)
-        elif kind == 6:        # REDFT11
-            v = 2 * np.sum(x * _cs((2 * j + 1) * (2 * k + 1), 4 * n, np.cos), axis=1)
-        elif kind == 7:        # RODFT00, logical N = 2(n + 1)
-            v = 2 * np.sum(x * _cs((j + 1) * (k + 1), n + 1, np.sin), axis=1)
+            c = _cs(j[:, 1:] * (2 * k + 1), 2 * n, np.cos)
+            f = lambda r: r[0] + 2 * np.sum(r[1:] * c, axis=1)
         elif kind == 8:        # RODFT01
-            v = sgn * x[n - 1] + 2 * np.sum(x[:n - 1] * _cs((j[:, :n - 1] + 1) * (2 * k + 1), 2 * n, np.sin), axis=1)
-        elif kind == 9:        # RODFT10
-            v = 2 * np.sum(x * _cs((2 * j + 1) * (k + 1), 2 * n, np.sin), axis=1)
-        elif kind == 10:       # RODFT11
-            v = 2 * np.sum(x * _cs((2 * j + 1) * (2 * k + 1), 4 * n, np.sin), axis=1)
+            c = _cs((j[:, :n - 1] + 1) * (2 * k + 1), 2 * n, np.sin)
+            f = lambda r: sgn * r[n - 1] + 2 * np.sum(r[:n - 1] * c, axis=1)
         else:
-            raise ValueError(kind)
-        out[k0:k0 + len(v)] = v
+            if kind == 5:      # REDFT10
+                c = _cs((2 * j + 1) * k, 2 * n, np.cos)
+            elif kind == 6:    # REDFT11
+                c = _cs((2 * j + 1) * (2 * k + 1), 4 * n, np.cos)
+            elif kind == 7:    # RODFT00, logical N = 2(n + 1)
+                c = _cs((j + 1) * (k + 1), n + 1, np.sin)
+            elif kind == 9:    # RODFT10
+                c = _cs((2 * j + 1) * (k + 1), 2 * n, np.sin)
+            elif kind == 10:   # RODFT11
+                c = _cs((2 * j + 1) * (2 * k + 1), 4 * n, np.sin)
+            else:
+                raise ValueError(kind)
+            f = lambda r: 2 * np.sum(r * c, axis=1)
+        for b in range(x.shape[0]):
+            out[b, k0:k0 + k.shape[0]] = f(x[b])
     return out
 
 

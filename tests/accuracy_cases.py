@@ -18,6 +18,21 @@ from util import ROOT, crand, oracle_c2r, oracle_dft, oracle_r2c, oracle_r2r, rr
 CSRC = os.path.join(ROOT, "fftw3_amd", "csrc")
 R2R_TAG = ["post-r2hc", "pre-hc2r", "post-dht", "post-e00", "post-e01", "post-e10", "post-e11",
            "post-o00", "post-o01", "post-o10", "post-o11"]
+# the one-trip real-rows kernels with r2r hooks (r2crows.hpp with r2r_epi.hpp): rows per workgroup R2CRGeom<R1, R2>::T
+# for each half length L, and per r2r kind the step's label and the r2r length n whose inner real DFT has 2L points
+R2R_ROWS_TILE = {64: 64, 128: 32, 256: 16, 512: 8, 1024: 4}
+R2R_ROWS = {0: ("r2c-rows+r2r-post", 2, 0), 2: ("r2c-rows+r2r-post", 2, 0), 5: ("r2c-rows+r2r-post", 2, 0),
+            9: ("r2c-rows+r2r-post", 2, 0), 3: ("r2c-rows+r2r-post", 1, 1), 7: ("r2c-rows+r2r-post", 1, -1),
+            1: ("c2r-rows+r2r-pre", 2, 0), 4: ("c2r-rows+r2r-pre+post", 2, 0), 8: ("c2r-rows+r2r-pre+post", 2, 0)}
+R2R_ROWS_ABSENT = ["(r2r-", "untangle", "tangle", "(copy"]
+
+
+def r2r_rows(L, k):
+    """(n, hm, tile, label) of r2r kind k on the one-trip rows kernel of half length L: two full tiles and a ragged
+    one; the label ends in the tile so that "r2r-pre" cannot match a "r2r-pre+post" step"""
+    name, mul, add = R2R_ROWS[k]
+    T = R2R_ROWS_TILE[L]
+    return mul * L + add, 2 * T + 3, T, "pass-%d/%s tile=%d" % (L, name, T)
 
 
 def _menu(name, nfields):
@@ -44,10 +59,13 @@ def _largest_fitting_hard_length(nb, lo):
 
 class Case(object):
     def __init__(self, fam, kind, shape, hm=1, sign=-1, labels=(), env=None, col=False, r2r=None, padded=False,
-                 slow=False, absent=()):
+                 slow=False, absent=(), tile=None, linf=False):
         self.fam, self.kind, self.shape, self.hm, self.sign = fam, kind, tuple(shape), hm, sign
         self.labels, self.absent, self.env = tuple(labels), tuple(absent), dict(env or {})
         self.col, self.r2r, self.padded, self.slow = col, r2r, padded, slow
+        # tile: the plan is one step of this tile, the batch two full tiles and a ragged one (check_plan);
+        # linf: the result also meets the relative L-infinity bound of util.TOL against the oracle (check_linf)
+        self.tile, self.linf = tile, linf
 
     @property
     def n(self):
@@ -158,6 +176,13 @@ def cases():
     for n in (16, 15, 1000, 243, 4096):
         for k in range(11):
             C.append(Case("r2r", "r2r", (n,), 3, r2r=k, labels=["r2r-" + R2R_TAG[k]]))
+    # r2r-rows: the nine kinds whose whole axis is one launch of the fused real-rows kernel (in-row gather of the
+    # Makhoul / padded sequence, real DFT, epilogue or prologue with the modulus-4n twiddle, DCT-III / DST-III store
+    # shuffle), every half length of the kernel, two full tiles and a ragged one
+    for L in sorted(R2R_ROWS_TILE):
+        for k in sorted(R2R_ROWS):
+            n, hm, T, lab = r2r_rows(L, k)
+            C.append(Case("r2r-rows", "r2r", (n,), hm, r2r=k, labels=[lab], absent=R2R_ROWS_ABSENT, tile=T, linf=True))
     # the single-device 1-D slab plan: slab_twiddle_kernel's global-position twiddles
     C.append(Case("slab1d", "slab", (1 << 22,), 1, labels=["pass-2048/reg3"], slow=True))
     return C
@@ -331,6 +356,7 @@ def run_gpu(case, x):
             full = [a.to_device(dev) for a in AR]
             ref = [t.clone() for t in full]
             p = prob.plan(fa, [t[a.lo:] for t, a in zip(full, AR)])
+            check_plan(case, p)
             p.execute()
             p.sync()
             torch.cuda.synchronize()
@@ -371,3 +397,23 @@ def check_labels(case, sprint):
         assert lab in sprint, (case.id, lab, sprint)
     for lab in case.absent:
         assert lab not in sprint, (case.id, lab, sprint)
+
+
+def check_plan(case, plan):
+    """a case that names its tile: the plan is that one step, and the batch has two full tiles and a ragged one"""
+    if case.tile is None:
+        return
+    st, T = plan.steps(), case.tile
+    assert len(st) == 1, (case.id, plan.sprint())
+    assert st[0].tile == T and case.hm > 2 * T and case.hm % T != 0, (case.id, st[0].tile, T, case.hm)
+
+
+def check_linf(case, got, x):
+    """for a case with linf set: the 1e-10 bar of the other modules, relative L-infinity against the oracle, which no
+    rms dilutes (one wrong element of any row, the ragged tile's included, fails it); returns the error"""
+    if not case.linf:
+        return None
+    from util import TOL, aerror
+    e = aerror(got, ref_oracle(case, x))
+    assert e <= TOL, (case.id, "relative L-infinity error against the oracle", e)
+    return e

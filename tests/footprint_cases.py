@@ -31,12 +31,14 @@ FAMILIES = {
     "pass1024": ["pass-1024/reg32x32"],
     "pass-2048x1024": ["pass-2048/reg3", "pass-1024/reg32x32"],
 }
+# the three one-trip r2r rows steps (accuracy_cases.R2R_ROWS); the tile follows, so that "pre" is not "pre+post"
+R2R_ROWS_STEPS = ["r2c-rows+r2r-post tile=", "c2r-rows+r2r-pre tile=", "c2r-rows+r2r-pre+post tile="]
 
 
 class FCase(AC.Case):
     def __init__(self, fam, kind, shape, hm, layout, sign=-1, labels=(), env=None, r2r=None, host=False, flags=0,
-                 absent=(), kinds=None):
-        AC.Case.__init__(self, fam, kind, shape, hm, sign, labels, env, r2r=r2r, absent=absent)
+                 absent=(), kinds=None, tile=None):
+        AC.Case.__init__(self, fam, kind, shape, hm, sign, labels, env, r2r=r2r, absent=absent, tile=tile)
         self.layout, self.host, self.flags, self.kinds = layout, host, flags, kinds
 
     @property
@@ -74,6 +76,9 @@ def problem(c):
         so = hs if kind == "r2c" else shape
         if name == "dense":
             return F.Problem(kind, shape, h, L(), L(), **kw)
+        if name == "dense-inplace":
+            assert kind in ("c2c", "r2r")
+            return F.Problem(kind, shape, h, L(), L(), inplace=True, **kw)
         if name == "embedded":
             ei, eo = _plus2(si), _plus2(so)
         else:
@@ -197,6 +202,20 @@ def cases():
             for name in ("gapped", "strided", "sparecol", "gapped-inplace"):
                 C.append(FCase("r2r", "r2r", (n,), 3, name, r2r=k, labels=["r2r-" + AC.R2R_TAG[k]]))
     C.append(FCase("r2r-nd", "r2r", (12, 1000), 2, "embedded", kinds=[5, 8]))
+    # r2r-rows: the one-trip real-rows kernels with r2r hooks at half lengths 128 and 1024 (tiles of 32 and 4 rows),
+    # the ragged batches of the accuracy matrix.  Only the dense case pins the step; which other layouts keep it is
+    # r2r_rows_steps' business
+    for half in (128, 1024):
+        for k in (0, 5, 9, 1, 4, 8, 3, 7):
+            n, hm, T, lab = AC.r2r_rows(half, k)
+            for name in ("dense", "gapped", "strided", "sparecol", "dense-inplace", "gapped-inplace"):
+                pin = dict(labels=[lab], absent=AC.R2R_ROWS_ABSENT, tile=T) if name == "dense" else {}
+                C.append(FCase("r2r-rows", "r2r", (n,), hm, name, r2r=k, **pin))
+    # the rows step as the last axis of a plan that another axis shares, embedded and in place
+    C.append(FCase("r2r-rows-nd", "r2r", (24, 256), 2, "embedded", kinds=[4, 5],
+                   labels=["pass-128/r2c-rows+r2r-post tile=32"]))
+    C.append(FCase("r2r-rows-nd", "r2r", (20, 256), 2, "dense-inplace", kinds=[9, 8],
+                   labels=["pass-128/c2r-rows+r2r-pre+post tile=32"]))
     return C
 
 
@@ -330,6 +349,7 @@ def run(case, x, execute=None):
         arrays = [a.user() for a in AR]
     with AC.knobs(case.env):
         plan = prob.plan(fa, arrays)
+        AC.check_plan(case, plan)
         res.sprint = plan.sprint()
         res.plan_steps = [(s.src_buf, s.dst_buf) for s in plan.steps()]
         res.preserved = None if prob.inplace else True
@@ -372,4 +392,18 @@ def family_labels(sprint_of):
         for f in FAMILIES:
             if s and f not in reached and all(lab in s for lab in FAMILIES[f]):
                 reached[f] = c.id
+    return reached
+
+
+def r2r_rows_steps(sprint_of):
+    """{step of R2R_ROWS_STEPS: id of the first non-dense r2r-rows case whose plan is that one step};
+    sprint_of(case) -> the case's sprint(), or None to pass the case over"""
+    reached = {}
+    for c in cases():
+        if c.fam != "r2r-rows" or c.dense:
+            continue
+        s = sprint_of(c)
+        for lab in R2R_ROWS_STEPS:
+            if s and lab not in reached and lab in s and len(s.strip().split("\n")) == 2:
+                reached[lab] = c.id
     return reached

@@ -177,6 +177,17 @@ def test_oracle_and_numpy_pass_the_gate_against_each_other(fam):
         assert max(eo, en) < 30 * A.U, (case.id, eo / A.U, en / A.U)
 
 
+def test_every_r2r_rows_case_plans_as_its_one_step():
+    """the 45 (half length, kind) pairs of the one-trip r2r rows kernels: each host plan is the one pinned step"""
+    rows = [c for c in AC.cases() if c.fam == "r2r-rows"]
+    assert len(set((c.shape, c.r2r) for c in rows)) == len(rows) == 5 * 9
+    for c in rows:
+        prob = AC._problem(c)
+        p = prob.plan(fa, [a.user() for a in prob.arenas()])
+        AC.check_plan(c, p)
+        AC.check_labels(c, p.sprint())
+
+
 # ---- the gate separates correct twiddle schemes from subtly wrong ones
 
 def _fft_radix2(x, tw):

@@ -140,6 +140,13 @@ def test_every_c2c_family_is_reached_by_a_non_dense_case():
     assert sorted(reached) == sorted(FC.FAMILIES), sorted(set(FC.FAMILIES) - set(reached))
 
 
+def test_every_r2r_rows_step_is_reached_by_a_non_dense_case():
+    reached = FC.r2r_rows_steps(_plan_on_host)
+    for lab, cid in sorted(reached.items()):
+        print("%-32s %s" % (lab, cid))
+    assert sorted(reached) == sorted(FC.R2R_ROWS_STEPS), sorted(set(FC.R2R_ROWS_STEPS) - set(reached))
+
+
 def test_case_ids_are_unique_and_references_are_shared():
     ids = [c.id for c in CASES]
     assert len(ids) == len(set(ids)) and len(ids) >= 300
@@ -237,6 +244,21 @@ def test_step_lists_write_only_the_footprint_and_preserve_the_input():
             assert all(dst != 0 for _, dst in r.plan_steps), (c.id, r.sprint)
         assert r.repeat, c.id
     assert {k for k, _, _ in seen} == {"c2c", "r2c", "c2r", "r2r"} and {r for _, r, _ in seen} == {1, 2, 3}
+
+
+def test_r2r_rows_cases_write_only_the_footprint_through_the_step_interpreter():
+    """the r2r-rows cases of the GPU matrix, pinned steps and tiles included, through the step interpreter"""
+    rows = [c for c in CASES if c.fam.startswith("r2r-rows")]
+    assert len(rows) == 2 * 8 * 6 + 2
+    for c in rows:
+        x = FC.make_input(c)
+        r = FC.run(c, x, execute=_interp)
+        AC.check_labels(c, r.sprint)
+        assert not any(r.violations), (c.id, r.violations, r.sprint)
+        assert aerror(r.got, _oracle_result(c, x)) < TOL, (c.id, r.sprint)
+        if not c.problem().inplace:
+            assert r.preserved, (c.id, r.sprint)
+        assert r.repeat, c.id
 
 
 def test_arena_layout():

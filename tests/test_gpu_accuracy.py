@@ -7,7 +7,8 @@ reference, and
 for the whole batch and, for n >= 1024, for every batch entry on its own (an error confined to a ragged last tile or
 one chunk is not diluted by the rest).  Every case also asserts the kernel its plan's sprint() shows, and its device
 arrays sit in the NaN-patterned arenas of tests/footprint.py: no word outside the output footprint may change and the
-input of an out-of-place plan must come back bit for bit.  This is in
+input of an out-of-place plan must come back bit for bit.  A case that names its tile also asserts that its plan is
+that one step with two full tiles and a ragged one, and a case with linf set the 1e-10 bar as well.  This is in
 addition to the 1e-10 checks of the other modules, which only see indexing bugs: a twiddle off by a few ulp passes
 those and fails this.  The slowest cases carry "slow" in their ids (-k slow selects them)."""
 import numpy as np
@@ -33,6 +34,7 @@ def test_rms_error_within_three_times_the_references(case):
     ratio = m["gpu"] / max(m["oracle"], m["numpy"], A.U / 2)
     print("%s gpu %.3f u oracle %.3f u numpy %.3f u ratio %.2f" % (case.id, m["gpu"] / A.U, m["oracle"] / A.U,
                                                                    m["numpy"] / A.U, ratio))
+    AC.check_linf(case, got, x)
     assert A.passes(m["gpu"], m["oracle"], m["numpy"]), (case.id, m["gpu"] / A.U, m["oracle"] / A.U,
                                                         m["numpy"] / A.U, sprint)
     if "per" in m:

@@ -62,3 +62,18 @@ def test_every_c2c_family_is_reached_by_a_non_dense_case_that_passed():
     for f, cid in sorted(reached.items()):
         print("%-24s %s" % (f, cid))
     assert sorted(reached) == sorted(FC.FAMILIES), sorted(set(FC.FAMILIES) - set(reached))
+
+
+def test_every_r2r_rows_step_is_reached_by_a_non_dense_case_that_passed():
+    """each of the three one-trip r2r rows steps is the whole plan of a non-dense case that executed and met the pass
+    condition (a lookup after the parametrised test; selected on its own, this test runs the in-place cases)"""
+    def sprint_of(c):
+        if c.id not in PASSED and not PASSED_ANY[0] and c.layout == "dense-inplace":
+            _run_and_check(c)
+        return PASSED.get(c.id)
+
+    PASSED_ANY = [bool(PASSED)]
+    reached = FC.r2r_rows_steps(sprint_of)
+    for lab, cid in sorted(reached.items()):
+        print("%-32s %s" % (lab, cid))
+    assert sorted(reached) == sorted(FC.R2R_ROWS_STEPS), sorted(set(FC.R2R_ROWS_STEPS) - set(reached))
