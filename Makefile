@@ -9,7 +9,7 @@ LIBDIR := fftw3_amd/lib
 CFLAGS := -O2 -fPIC -std=gnu99 -Wall -Wextra -Iinclude -I$(CSRC)
 HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -std=c++17 -Wall
 
-OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgr.o
+OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/exec.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgr.o
 
 all: $(LIBDIR)/libfftw3_amd.so
 
@@ -80,13 +80,20 @@ oracle:
 
 # host-only sanitizer check of the two-trip c2r planner path: the C sources under ASan + UBSan, the HIP units (host-side
 # tables only) from the ordinary library.  Planning needs no device.
-SANSRC := $(CSRC)/api.c $(CSRC)/planner.c $(CSRC)/sharded.c $(CSRC)/slab.c $(CSRC)/slab1d.c $(CSRC)/hostmath.c
+SANSRC := $(CSRC)/api.c $(CSRC)/planner.c $(CSRC)/exec.c $(CSRC)/sharded.c $(CSRC)/slab.c $(CSRC)/slab1d.c $(CSRC)/hostmath.c
 san-c2r: $(LIBDIR)/libfftw3_amd.so
 	mkdir -p build
 	$(CC) -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -I$(CSRC) tools/san/plan_c2r_decimated.c $(SANSRC) -o build/plan_c2r_decimated_san -L$(LIBDIR) -lfftw3_amd -Wl,-rpath,$(abspath $(LIBDIR)) -lm -lpthread -ldl
 	./build/plan_c2r_decimated_san
 
-clean:
-	rm -f $(OBJS) $(LIBDIR)/*.so* build/plan_c2r_decimated_san
+# the executor on a CPU against a recording fake of the runtime calls (tools/trace/exec_trace.c): every case under
+# ASan + UBSan, each in its own process
+san-exec: $(LIBDIR)/libfftw3_amd.so
+	mkdir -p build
+	$(CC) -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -I$(CSRC) tools/trace/exec_trace.c $(SANSRC) -o build/exec_trace_san -L$(LIBDIR) -lfftw3_amd -Wl,-rpath,$(abspath $(LIBDIR)) -lm -lpthread -ldl
+	set -e; for c in $$(./build/exec_trace_san --list); do ./build/exec_trace_san $$c > /dev/null; done
 
-.PHONY: all oracle clean san-c2r
+clean:
+	rm -f $(OBJS) $(LIBDIR)/*.so* build/plan_c2r_decimated_san build/exec_trace_san
+
+.PHONY: all oracle clean san-c2r san-exec

@@ -109,6 +109,17 @@ enum {
                            ordinary in-place plan on the input strides, then the in-place step */
 };
 
+/* plan.sched: how the chunks of the batch are enqueued (exec.c: choose_schedule picks one when the plan is set up on
+   the device; a plan that is not set up yet is SERIAL) */
+enum {
+    FA_SCHED_SERIAL = 0,    /* chunk after chunk on the caller's stream, one scratch slot */
+    FA_SCHED_PAIR,          /* 1024 x 1024 plan: pass 2 of chunk c-1 and pass 1 of chunk c in one launch (fa_hip_launch_pair1024),
+                               two scratch slots; becomes SERIAL when the kernel refuses the plan's first launch */
+    FA_SCHED_PIPE,          /* two-stream chunk pipeline: stage A (steps [0, split)) of chunk c+1 on pstream[0] overlaps stage B
+                               (steps [split, nsteps)) of chunk c on pstream[1]; three scratch slots */
+    FA_SCHED_LANES          /* chunk lanes (see fa_cfg.lanes): the streams are pstream[0 .. lanes) */
+};
+
 struct fftw_plan_s {
     int type;                   /* FA_C2C / FA_R2C / FA_C2R / FA_R2R */
     int kinds[FA_MAXRANK];      /* FA_R2R: fftw_r2r_kind of every dim */
@@ -148,12 +159,9 @@ struct fftw_plan_s {
     int dev_ready;
     pthread_mutex_t lock;       /* fftw_execute is thread-safe in the reference; the plan's scratch is not shareable */
 
-    /* chunk pipeline: stage A (steps [0, split)) of chunk c+1 overlaps stage B
-       (steps [split, nsteps)) of chunk c on a second stream; each chunk works
-       in scratch slot c % nslots */
-    int nslots, split;
-    int pair;                   /* both passes of the 1024 x 1024 plan in one launch per chunk (fa_hip_launch_pair1024) */
-    int lanes;                  /* > 1: chunk lanes (see fa_cfg.lanes); the streams are pstream[0 .. lanes) */
+    int sched;                  /* FA_SCHED_* */
+    int nslots, split;          /* scratch slots (chunk c works in slot c % nslots); FA_SCHED_PIPE: first step of stage B */
+    int lanes;                  /* FA_SCHED_LANES: number of lanes, 1 otherwise */
     void *pstream[FA_MAXLANES];
     void *ev_a[4], *ev_b[4], *ev_begin, *ev_end[FA_MAXLANES];
     int failed;
@@ -190,8 +198,6 @@ int  fa_factor_passes_pref(i64 n, int max_passes, i64 lmax_single, i64 lmax_mult
 struct fftw_plan_s *fa_plan_new(void);
 void fa_plan_free(struct fftw_plan_s *p);
 int  fa_build(struct fftw_plan_s *p);     /* steps from p->type/dims/hdims; 0 on success */
-int  fa_device_init(struct fftw_plan_s *p);
-void fa_run(struct fftw_plan_s *p, double *ri, double *ii, double *ro, double *io);
 char *fa_sprint(const struct fftw_plan_s *p);
 fa_cfg fa_default_cfg(void);
 /* 1 and *t when the loops l[0 .. nl) (strides in doubles, `unit` doubles per element) are a transposition the tile
@@ -202,6 +208,13 @@ int fa_match_transpose(const fa_dim *l, int nl, i64 unit, fa_transp *t);
 /* 1 when *t is square with equal leading dimensions, every batch loop has the same stride on both sides and the
    matrices of the batch do not overlap: the in-place step applies */
 int fa_transp_inplace_ok(const fa_transp *t);
+
+/* exec.c */
+int  fa_device_init(struct fftw_plan_s *p);      /* tables, schedule, scratch; 0 on success */
+/* gives back everything fa_device_init and the executions created; fa_plan_free calls it.  Hidden: the library's
+   dynamic symbols stay what they were */
+__attribute__((visibility("hidden"))) void fa_exec_release(struct fftw_plan_s *p);
+void fa_run(struct fftw_plan_s *p, double *ri, double *ii, double *ro, double *io);
 
 /* api.c */
 struct fftw_plan_s *fa_unaligned_twin(const struct fftw_plan_s *p);

@@ -13,6 +13,9 @@
  *   - rdft2 via half-length complex DFT + untangle (ct_hc2c A.c:5579-5590)
  * A CPU cost model is meaningless on the GPU, so there is no search: the
  * decomposition is a function of n and of which index is contiguous.
+ *
+ * Planning only: the plan object, its tables, fa_build and fa_sprint.  Bringing a plan onto the device and running
+ * it is exec.c.
  */
 #include <math.h>
 #include <stdarg.h>
@@ -108,31 +111,7 @@ void fa_plan_free(plan *p) {
     int i;
     if (!p) return;
     if (p->alt) { fa_plan_free(p->alt); p->alt = NULL; }
-    {
-        /* device resources may exist without dev_ready (fa_device_init gave up half way: out of device memory) */
-        int any = p->dev_ready || p->stage_in || p->stage_out || p->hstream[0] || p->pstream[0];
-        for (i = 0; i < p->ntabs && !any; ++i) any = p->tabs[i].dev != NULL;
-        for (i = 2; i < p->nbufs && !any; ++i) any = p->dbuf[i] != NULL;
-        if (!any) goto host_only;
-    }
-    {
-        fa_hip_stream_sync(p->stream);
-        for (i = 0; i < p->ntabs; ++i) fa_hip_free(p->tabs[i].dev);
-        for (i = 2; i < p->nbufs; ++i) fa_hip_free(p->dbuf[i]);
-        fa_hip_free(p->stage_in);
-        fa_hip_free(p->stage_out);
-        if (p->hstream[0]) fa_hip_stream_destroy(p->hstream[0]);
-        if (p->hstream[1]) fa_hip_stream_destroy(p->hstream[1]);
-        if (p->pstream[0]) {
-            for (i = 0; i < 4; ++i) { if (p->ev_a[i]) fa_hip_event_destroy(p->ev_a[i]); if (p->ev_b[i]) fa_hip_event_destroy(p->ev_b[i]); }
-            fa_hip_event_destroy(p->ev_begin);
-            for (i = 0; i < FA_MAXLANES; ++i) {
-                if (p->ev_end[i]) fa_hip_event_destroy(p->ev_end[i]);
-                if (p->pstream[i]) fa_hip_stream_destroy(p->pstream[i]);
-            }
-        }
-    }
-host_only:
+    fa_exec_release(p);        /* the device half: tables, scratch, staging, streams and events (exec.c) */
     for (i = 0; i < p->ntabs; ++i) free(p->tabs[i].host);
     free(p->steps);
     pthread_mutex_destroy(&p->lock);
@@ -2540,455 +2519,6 @@ static int fa_build_steps_sized(plan *p) {
         }
     }
     return 0;
-}
-
-/* ---------------------------------------------------------------- device */
-
-static plan *make_c2c_1d_contig(i64 n) {
-    plan *q = fa_plan_new();
-    q->type = FA_C2C;
-    q->sign = FFTW_FORWARD;
-    q->rank = 1;
-    q->dims[0].n = n; q->dims[0].is = 2; q->dims[0].os = 2;
-    q->hrank = 0;
-    if (fa_build(q)) { fa_plan_free(q); return NULL; }
-    return q;
-}
-
-int fa_device_init(plan *p) {
-    int i;
-    if (p->dev_ready) return 0;
-    if (fa_hip_device_count() <= 0) {
-        fprintf(stderr, "fftw3_amd: no HIP device available: this executor has no CPU "
-                        "fallback; fftw_execute cannot run\n");
-        return -1;
-    }
-    for (i = 0; i < p->ntabs; ++i) {
-        fa_table *t = &p->tabs[i];
-        size_t bytes = (size_t)t->len * (t->kind == FA_TAB_PERM ? sizeof(i64) : 2 * sizeof(double));
-        if (t->dev) continue;
-        t->dev = fa_hip_malloc(bytes);
-        if (!t->dev) return -1;
-        if (t->kind == FA_TAB_DFT_OF) continue;    /* second sweep */
-        fa_hip_memcpy_h2d(t->dev, t->host, bytes, p->stream);
-    }
-    fa_hip_stream_sync(p->stream);
-    for (i = 0; i < p->ntabs; ++i) {
-        fa_table *t = &p->tabs[i];
-        if (t->kind != FA_TAB_DFT_OF) continue;
-        {
-            /* the convolution kernel is itself a DFT: compute it with a
-               nested plan on the device, keep a host copy for introspection */
-            plan *q = make_c2c_1d_contig(t->n);
-            size_t bytes = (size_t)t->len * 2 * sizeof(double);
-            if (!q) return -1;
-            q->stream = p->stream;
-            fa_run(q, (double *)p->tabs[t->src].dev, (double *)p->tabs[t->src].dev + 1,
-                   (double *)t->dev, (double *)t->dev + 1);
-            if (!t->host) t->host = malloc(bytes);
-            fa_hip_memcpy_d2h(t->host, t->dev, bytes, p->stream);
-            fa_hip_stream_sync(p->stream);
-            fa_plan_free(q);
-        }
-    }
-    /* chunk pipeline: worth it when there are several chunks of >= 2 steps */
-    p->nslots = 1;
-    p->pair = 0;
-    {
-        /* batched 1024 x 1024: pass 2 of chunk c-1 and pass 1 of chunk c share a launch (two scratch slots) */
-        static int pair_mode = -1;     /* FFTW_AMD_PAIR=0 switches it off */
-        if (pair_mode < 0) { const char *e = getenv("FFTW_AMD_PAIR"); pair_mode = e ? atoi(e) : 1; }
-        if (pair_mode && !p->cfg.pipeline && p->cfg.lanes <= 1 && p->nsteps == 2 && p->nbufs == 3 && p->chunk > 0 && p->chunk < p->batch &&
-            !p->single_chunk &&
-            p->steps[0].kind == FFTW_AMD_STEP_PASS && p->steps[1].kind == FFTW_AMD_STEP_PASS &&
-            p->steps[0].variant == FFTW_AMD_K_P1024 && p->steps[1].variant == FFTW_AMD_K_P1024 &&
-            p->steps[0].src_buf == 0 && p->steps[0].dst_buf == 2 && p->steps[1].src_buf == 2 && p->steps[1].dst_buf == 1 &&
-            p->steps[0].tw_n == 0 && p->steps[1].tw_n != 0 && (p->steps[1].flags & FFTW_AMD_F_TW_IN) &&
-            p->steps[0].tile_lo_n <= 1 && p->steps[1].tile_lo_n <= 1 &&
-            p->steps[0].batch_dim >= 0 && p->steps[1].batch_dim >= 0) {
-            p->pair = 1;
-            p->nslots = 2;
-        }
-    }
-    if (!p->pair && p->chunk > 0 && p->nsteps >= 2 && (p->batch + p->chunk - 1) / p->chunk >= 3 &&
-        !p->single_chunk && p->cfg.pipeline) {
-        i64 per = 0;
-        for (i = 2; i < p->nbufs; ++i) per += p->buf_reals[i];
-        if (per > 0 && (size_t)per * sizeof(double) * 3 <= ((size_t)8 << 30)) {
-            p->nslots = 3;
-            p->split = p->nsteps / 2;
-            p->pstream[0] = fa_hip_stream_create();
-            p->pstream[1] = fa_hip_stream_create();
-            for (i = 0; i < 4; ++i) { p->ev_a[i] = fa_hip_event_create(); p->ev_b[i] = fa_hip_event_create(); }
-            p->ev_begin = fa_hip_event_create();
-            p->ev_end[0] = fa_hip_event_create();
-            p->ev_end[1] = fa_hip_event_create();
-        }
-    }
-    /* chunk lanes: chunk c runs all its steps, in order, on stream c % lanes in scratch slot c % lanes; the
-       lanes share the machine, so the tail of one lane's launch overlaps the other lane's next launch and
-       no dependency crosses the lanes */
-    p->lanes = 1;
-    if (!p->pair && p->nslots == 1 && p->cfg.lanes > 1 && p->chunk > 0 && p->nsteps >= 2 && p->nbufs > 2 &&
-        !p->single_chunk && (p->batch + p->chunk - 1) / p->chunk >= 2) {
-        i64 nch = (p->batch + p->chunk - 1) / p->chunk, per = 0;
-        for (i = 2; i < p->nbufs; ++i) per += p->buf_reals[i];
-        /* a chunk whose scratch is beyond the budget anyway (one transform with hundreds of MB of scratch: two of
-           them in flight leave nothing on the die) gains nothing from a second lane and loses to the doubled
-           footprint -- cfg4, n = 15 375 360, 246 MB of scratch per transform: 67.0 ms serial, 71 ... 76 ms with two
-           lanes; one 4096 x 4096 image (256 MiB): 14.7 serial, 14.5 with two (tools/perf/perf_lanes_gate.sh) */
-        if ((size_t)per * sizeof(double) > p->cfg.chunk_bytes) nch = 0;
-        p->lanes = p->cfg.lanes > FA_MAXLANES ? FA_MAXLANES : p->cfg.lanes;
-        if (p->lanes > nch) p->lanes = nch > 0 ? (int)nch : 1;
-        p->nslots = p->lanes;
-        for (i = 0; p->lanes > 1 && i < p->lanes; ++i) { p->pstream[i] = fa_hip_stream_create(); p->ev_end[i] = fa_hip_event_create(); }
-        if (p->lanes > 1) p->ev_begin = fa_hip_event_create();
-    }
-    for (i = 2; i < p->nbufs; ++i)
-        if (!p->dbuf[i]) {
-            p->dbuf[i] = (double *)fa_hip_malloc((size_t)p->buf_reals[i] * sizeof(double) * (size_t)p->nslots);
-            if (!p->dbuf[i]) return -1;
-        }
-    p->dev_ready = 1;
-    return 0;
-}
-
-/* How a host array is laid out in its device staging buffer.  Offsets count doubles relative to
-   the pointer of the "real" part; im is the caller's real -> imaginary distance. */
-typedef struct {
-    int two;        /* 1: two packed planes of `span` doubles each, 0: one span [lo, hi] covering both parts */
-    i64 lo, hi;     /* touched offsets (two: of each plane; one span: of both parts together) */
-    i64 span;
-    i64 im_dev;     /* real -> imaginary distance inside the staging buffer */
-} stage_layout;
-
-static stage_layout stage_layout_of(i64 lo, i64 hi, i64 im) {
-    stage_layout L;
-    L.span = hi - lo + 1;
-    L.two = im != 0 && iabs(im) >= L.span;
-    if (L.two) {
-        L.lo = lo; L.hi = hi;
-        L.im_dev = im > 0 ? L.span : -L.span;
-    } else {
-        L.lo = im < 0 ? lo + im : lo;
-        L.hi = im > 0 ? hi + im : hi;
-        L.span = L.hi - L.lo + 1;
-        L.im_dev = im;
-    }
-    return L;
-}
-static size_t stage_bytes(const stage_layout *L) { return (size_t)L->span * (L->two ? 2 : 1) * sizeof(double); }
-/* device address that plays the role of the caller's real-part pointer */
-static double *stage_origin(const stage_layout *L, double *st) {
-    return st - L->lo + ((L->two && L->im_dev < 0) ? L->span : 0);
-}
-static void stage_h2d(const stage_layout *L, double *st, const double *re, i64 im, void *stream) {
-    double *o = stage_origin(L, st);
-    if (L->two) {
-        fa_hip_memcpy_h2d(o + L->lo, re + L->lo, (size_t)L->span * sizeof(double), stream);
-        fa_hip_memcpy_h2d(o + L->im_dev + L->lo, re + im + L->lo, (size_t)L->span * sizeof(double), stream);
-    } else {
-        fa_hip_memcpy_h2d(o + L->lo, re + L->lo, (size_t)L->span * sizeof(double), stream);
-    }
-}
-static void stage_d2h(const stage_layout *L, double *st, double *re, i64 im, void *stream) {
-    double *o = stage_origin(L, st);
-    if (L->two) {
-        fa_hip_memcpy_d2h(re + L->lo, o + L->lo, (size_t)L->span * sizeof(double), stream);
-        fa_hip_memcpy_d2h(re + im + L->lo, o + L->im_dev + L->lo, (size_t)L->span * sizeof(double), stream);
-    } else {
-        fa_hip_memcpy_d2h(re + L->lo, o + L->lo, (size_t)L->span * sizeof(double), stream);
-    }
-}
-
-static double *stage_buf(double **slot, size_t *have, size_t need) {
-    if (*have < need) {
-        fa_hip_free(*slot);
-        *slot = (double *)fa_hip_malloc(need);
-        if (!*slot) {
-            fprintf(stderr, "fftw3_amd: no device memory to stage the host arrays of this execution\n");
-            abort();
-        }
-        *have = need;
-    }
-    return *slot;
-}
-
-/* per-step HIP-event timing of one execution: p->prof_ms / p->prof_launches, set by
-   fftw_amd_execute_profiled under the plan's lock (never process-wide: another plan's
-   execute on another thread must not see them) */
-
-static void fa_run_locked(plan *p, double *ri, double *ii, double *ro, double *io);
-
-/* serialised per plan: concurrent fftw_execute calls on one plan are legal in the
-   reference (A.c:433, re-entrant executors) but here they share scratch and streams */
-void fa_run(plan *p, double *ri, double *ii, double *ro, double *io) {
-    pthread_mutex_lock(&p->lock);
-    /* New-array execution on arrays aligned differently from the plan's own (a caller error by FFTW's rules,
-       fftw3.h "new-array execute"): the plan may hold steps whose kernels rely on the 16-byte alignment it
-       saw at planning time and have no other executor.  Run the FFTW_UNALIGNED twin instead -- same problem,
-       same tables' values, only kernels that serve every alignment -- rather than abort() inside a library. */
-    if (!(p->flags & FFTW_UNALIGNED) && p->ri && p->ro && p->batch > 0 &&
-        ((((size_t)ri ^ (size_t)p->ri) | ((size_t)ii ^ (size_t)p->ii) | ((size_t)ro ^ (size_t)p->ro) | ((size_t)io ^ (size_t)p->io)) & 15)) {
-        if (!p->alt) p->alt = fa_unaligned_twin(p);
-        if (p->alt) {
-            p->alt->stream = p->stream;
-            fa_run_locked(p->alt, ri, ii, ro, io);
-            pthread_mutex_unlock(&p->lock);
-            return;
-        }
-    }
-    fa_run_locked(p, ri, ii, ro, io);
-    pthread_mutex_unlock(&p->lock);
-}
-
-static void fa_run_locked(plan *p, double *ri, double *ii, double *ro, double *io) {
-    double *bufs[FA_MAXBUF];
-    void *tabs[FA_MAXTAB];
-    int i, in_host = 0, out_host = 0, host_inplace = 0, hpipe = 0;
-    i64 cs, nhchunks = 0, hp_ibs = 0, hp_obs = 0, hp_ispan = 0, hp_ospan = 0;
-    void **ev_in = NULL, **ev_out = NULL;
-    i64 in_im = ii - ri, out_im = io - ro, out_im_host = 0;
-    stage_layout Lin, Lout;
-    double *din = ri, *dout = ro;
-    i64 in_span_lo = p->in_lo, in_span_hi = p->in_hi;
-    i64 out_span_lo = p->out_lo, out_span_hi = p->out_hi;
-
-    if (p->batch == 0) return;
-    if (fa_device_init(p)) abort();
-
-    if (FA_REAL_IN(p->type)) in_im = 0;
-    if (FA_REAL_OUT(p->type)) out_im = 0;
-
-    /* plain host arrays are staged through device copies (slow path, PCIe).  A split array whose
-       imaginary plane lies beyond the real one (|im| >= span: typically two separate allocations,
-       the usual fftw_plan_guru_split_dft call) is staged as two packed planes -- never as one span
-       from the lower to the upper plane, which would read and write whatever the caller keeps
-       between the two allocations. */
-    in_host = !fa_hip_is_device_ptr(ri);
-    out_host = !fa_hip_is_device_ptr(ro);
-    Lin = stage_layout_of(in_span_lo, in_span_hi, in_im);
-    Lout = stage_layout_of(out_span_lo, out_span_hi, out_im);
-    host_inplace = in_host && out_host && ro == ri && (io == ii || FA_REAL_OUT(p->type) || FA_REAL_IN(p->type));
-    if (host_inplace) {
-        /* both views share one staging image: same plane layout, union of the spans */
-        if (Lin.two != Lout.two || (Lin.two && (Lin.lo != Lout.lo || Lin.hi != Lout.hi || Lin.im_dev != Lout.im_dev))) {
-            fprintf(stderr, "fftw3_amd: in-place execution on host arrays whose input and output views have "
-                            "different split layouts is not supported\n");
-            abort();
-        }
-        if (!Lin.two) {
-            if (Lout.lo < Lin.lo) Lin.lo = Lout.lo;
-            if (Lout.hi > Lin.hi) Lin.hi = Lout.hi;
-            Lin.span = Lin.hi - Lin.lo + 1;
-            Lout.lo = Lin.lo; Lout.hi = Lin.hi; Lout.span = Lin.span;
-        }
-    }
-    /* Host pipeline: a batch that is dense on both sides (every transform's span below the batch stride) and
-       runs in several chunks is staged chunk by chunk on two copy streams -- upload of chunk c+1, compute of
-       chunk c and download of chunk c-1 overlap, so an unmodified host caller sees max(H2D, D2H) of the PCIe
-       link instead of their sum plus the compute.  Everything else is staged whole, as before. */
-    if (in_host && out_host && !host_inplace && !Lin.two && !Lout.two && p->hrank == 1 && !p->prof_ms &&
-        p->chunk > 0 && p->chunk < p->batch && !p->single_chunk && !(p->nslots > 1 && p->pstream[0] && p->lanes <= 1)) {
-        const i64 B = p->batch, ibs = p->hdims[0].is, obs = p->hdims[0].os;
-        const i64 it_span = Lin.span - (B - 1) * ibs, ot_span = Lout.span - (B - 1) * obs;   /* one transform's span */
-        static int hp_mode = -1;        /* FFTW_AMD_HOST_PIPELINE=0 switches it off */
-        if (hp_mode < 0) { const char *e = getenv("FFTW_AMD_HOST_PIPELINE"); hp_mode = e ? atoi(e) : 1; }
-        if (hp_mode && ibs > 0 && obs > 0 && it_span > 0 && ot_span > 0 && it_span <= ibs && ot_span <= obs &&
-            Lout.span == p->out_written) {
-            hpipe = 1;
-            hp_ibs = ibs; hp_obs = obs; hp_ispan = it_span; hp_ospan = ot_span;
-            nhchunks = (B + p->chunk - 1) / p->chunk;
-            if (!p->hstream[0]) { p->hstream[0] = fa_hip_stream_create(); p->hstream[1] = fa_hip_stream_create(); }
-            ev_in = (void **)calloc((size_t)nhchunks, sizeof(void *));
-            ev_out = (void **)calloc((size_t)nhchunks, sizeof(void *));
-        }
-    }
-    if (in_host) {
-        double *st = stage_buf(&p->stage_in, &p->stage_in_bytes, stage_bytes(&Lin));
-        din = stage_origin(&Lin, st);
-        if (hpipe) {
-            /* uploads are queued now, in chunk order, behind whatever the caller's stream already holds */
-            i64 c;
-            void *e0 = fa_hip_event_create();
-            fa_hip_event_record(e0, p->stream);
-            fa_hip_stream_wait_event(p->hstream[0], e0);
-            fa_hip_stream_wait_event(p->hstream[1], e0);
-            fa_hip_event_destroy(e0);
-            for (c = 0; c < nhchunks; ++c) {
-                const i64 c0 = c * p->chunk, cn = (p->batch - c0 < p->chunk) ? p->batch - c0 : p->chunk;
-                const i64 lo = Lin.lo + c0 * hp_ibs, len = (cn - 1) * hp_ibs + hp_ispan;
-                fa_hip_memcpy_h2d(din + lo, ri + lo, (size_t)len * sizeof(double), p->hstream[0]);
-                ev_in[c] = fa_hip_event_create();
-                fa_hip_event_record(ev_in[c], p->hstream[0]);
-            }
-        } else {
-            stage_h2d(&Lin, st, ri, in_im, p->stream);
-        }
-        in_im = Lin.im_dev;
-    }
-    if (out_host) {
-        if (host_inplace) {
-            dout = din;
-        } else {
-            double *st = stage_buf(&p->stage_out, &p->stage_out_bytes, stage_bytes(&Lout));
-            /* gaps between output elements must survive the round trip */
-            if ((i64)(stage_bytes(&Lout) / sizeof(double)) != p->out_written)
-                stage_h2d(&Lout, st, ro, out_im, p->stream);
-            dout = stage_origin(&Lout, st);
-        }
-        out_im_host = out_im;
-        out_im = Lout.im_dev;
-    }
-
-    bufs[0] = din;
-    bufs[1] = dout;
-    for (i = 2; i < p->nbufs; ++i) bufs[i] = p->dbuf[i];
-    for (i = 0; i < p->ntabs; ++i) tabs[i] = p->tabs[i].dev;
-
-    if (p->pair) {
-        /* launch k: pass 2 of chunk k-1 (scratch slot (k-1) & 1) + pass 1 of chunk k (slot k & 1) */
-        const i64 nchunks = (p->batch + p->chunk - 1) / p->chunk;
-        i64 k;
-        int ok = 1;
-        for (k = 0; k <= nchunks && ok; ++k) {
-            double *sb1[FA_MAXBUF], *sb2[FA_MAXBUF];
-            fftw_amd_step_desc d1 = p->steps[0], d2 = p->steps[1];
-            const i64 cs1 = k * p->chunk, cs2 = (k - 1) * p->chunk;
-            const i64 cn1 = k < nchunks ? (p->batch - cs1 < p->chunk ? p->batch - cs1 : p->chunk) : 0;
-            const i64 cn2 = k > 0 ? (p->batch - cs2 < p->chunk ? p->batch - cs2 : p->chunk) : 0;
-            void *e0 = NULL, *e1 = NULL;
-            sb1[0] = sb2[0] = bufs[0];
-            sb1[1] = sb2[1] = bufs[1];
-            sb1[2] = bufs[2] + (i64)(k & 1) * p->buf_reals[2];
-            sb2[2] = bufs[2] + (i64)((k + 1) & 1) * p->buf_reals[2];
-            if (d1.src_im == p->in_im && !FA_REAL_IN(p->type)) d1.src_im = in_im;
-            if (d2.dst_im == p->out_im && !FA_REAL_OUT(p->type)) d2.dst_im = out_im;
-            if (p->prof_ms) { e0 = fa_hip_event_create(); e1 = fa_hip_event_create(); fa_hip_event_record(e0, p->stream); }
-            if (hpipe && k < nchunks) fa_hip_stream_wait_event(p->stream, ev_in[k]);     /* chunk k is on the device */
-            if (fa_hip_launch_pair1024(&d2, sb2, cs2, cn2, &d1, sb1, cs1, cn1, tabs, p->stream)) {
-                if (k == 0) { ok = 0; }          /* not the pair the kernel is built for: ordinary launches below */
-                else abort();
-            }
-            if (hpipe && ok && k > 0) {
-                /* chunk k-1 is complete: download it while the next launches run */
-                const i64 lo = Lout.lo + cs2 * hp_obs, len = (cn2 - 1) * hp_obs + hp_ospan;
-                ev_out[k - 1] = fa_hip_event_create();
-                fa_hip_event_record(ev_out[k - 1], p->stream);
-                fa_hip_stream_wait_event(p->hstream[1], ev_out[k - 1]);
-                fa_hip_memcpy_d2h(ro + lo, dout + lo, (size_t)len * sizeof(double), p->hstream[1]);
-            }
-            if (p->prof_ms) {
-                fa_hip_event_record(e1, p->stream);
-                fa_hip_stream_sync(p->stream);
-                if (ok) { p->prof_ms[0] += (double)fa_hip_event_elapsed_ms(e0, e1); p->prof_launches[0] += 1; }
-                fa_hip_event_destroy(e0);
-                fa_hip_event_destroy(e1);
-            }
-        }
-        if (!ok) p->pair = 0;
-    }
-    if (!p->pair) {
-        i64 nchunks = (p->batch + p->chunk - 1) / p->chunk, ev = 0, c = 0;
-        void **events = NULL;
-        const int pipe = p->nslots > 1 && p->pstream[0] && p->lanes <= 1;
-        /* profiled executions keep the lanes: the HIP events around a launch sit on the lane's own stream and time
-           the launch as it really runs, beside the other lane's (rocprofv3's kernel durations see the same) */
-        const int lanes = p->lanes > 1 ? p->lanes : 1;
-        if (p->prof_ms) events = (void **)malloc(sizeof(void *) * (size_t)(2 * nchunks * p->nsteps));
-        if (pipe || lanes > 1) {
-            /* the side streams start after everything already queued on the caller's stream */
-            fa_hip_event_record(p->ev_begin, p->stream);
-            for (i = 0; i < (pipe ? 2 : lanes); ++i) fa_hip_stream_wait_event(p->pstream[i], p->ev_begin);
-        }
-        for (cs = 0; cs < p->batch; cs += p->chunk, ++c) {
-            i64 cn = p->batch - cs < p->chunk ? p->batch - cs : p->chunk;
-            double *sb[FA_MAXBUF];
-            int slot = pipe ? (int)(c % p->nslots) : (lanes > 1 ? (int)(c % lanes) : 0);
-            void *lane_st = lanes > 1 ? p->pstream[c % lanes] : p->stream;
-            sb[0] = bufs[0];
-            sb[1] = bufs[1];
-            for (i = 2; i < p->nbufs; ++i) sb[i] = bufs[i] + (i64)slot * p->buf_reals[i];
-            if (hpipe) fa_hip_stream_wait_event(lane_st, ev_in[c]);
-            for (i = 0; i < p->nsteps; ++i) {
-                fftw_amd_step_desc d = p->steps[i];
-                void *st = lane_st;
-                if (pipe) {
-                    st = p->pstream[i < p->split ? 0 : 1];
-                    /* stage A reuses a slot only after stage B of its previous user is done */
-                    if (i == 0 && c >= p->nslots) fa_hip_stream_wait_event(st, p->ev_b[slot]);
-                    if (i == p->split) fa_hip_stream_wait_event(st, p->ev_a[slot]);
-                }
-                /* split-array callers may pass different re/im distances per call */
-                if (d.src_buf == 0 && !FA_REAL_IN(p->type) && d.src_im == p->in_im) d.src_im = in_im;
-                if (d.dst_buf == 1 && !FA_REAL_OUT(p->type) && d.dst_im == p->out_im) d.dst_im = out_im;
-                if (events) { events[ev] = fa_hip_event_create(); fa_hip_event_record(events[ev++], st); }
-                if (fa_hip_launch_step(&d, sb, tabs, cs, cn, st)) abort();
-                if (events) { events[ev] = fa_hip_event_create(); fa_hip_event_record(events[ev++], st); }
-                if (pipe && i == p->split - 1) fa_hip_event_record(p->ev_a[slot], st);
-                if (pipe && i == p->nsteps - 1) fa_hip_event_record(p->ev_b[slot], st);
-            }
-            if (hpipe && !ev_out[c]) {
-                const i64 lo = Lout.lo + cs * hp_obs, len = (cn - 1) * hp_obs + hp_ospan;
-                ev_out[c] = fa_hip_event_create();
-                fa_hip_event_record(ev_out[c], lane_st);
-                fa_hip_stream_wait_event(p->hstream[1], ev_out[c]);
-                fa_hip_memcpy_d2h(ro + lo, dout + lo, (size_t)len * sizeof(double), p->hstream[1]);
-            }
-        }
-        if (pipe || lanes > 1) {
-            /* the caller's stream continues after the side streams have drained */
-            for (i = 0; i < (pipe ? 2 : lanes); ++i) {
-                fa_hip_event_record(p->ev_end[i], p->pstream[i]);
-                fa_hip_stream_wait_event(p->stream, p->ev_end[i]);
-            }
-        }
-        if (events) {
-            fa_hip_stream_sync(p->stream);
-            ev = 0;
-            for (c = 0; c < nchunks; ++c)
-                for (i = 0; i < p->nsteps; ++i) {
-                    p->prof_ms[i] += (double)fa_hip_event_elapsed_ms(events[ev], events[ev + 1]);
-                    p->prof_launches[i] += 1;
-                    fa_hip_event_destroy(events[ev]);
-                    fa_hip_event_destroy(events[ev + 1]);
-                    ev += 2;
-                }
-            free(events);
-        }
-    }
-
-    if (hpipe) {
-        i64 c;
-        fa_hip_stream_sync(p->stream);
-        fa_hip_stream_sync(p->hstream[1]);
-        for (c = 0; c < nhchunks; ++c) {
-            if (ev_in[c]) fa_hip_event_destroy(ev_in[c]);
-            if (ev_out[c]) fa_hip_event_destroy(ev_out[c]);
-        }
-        free(ev_in);
-        free(ev_out);
-        return;
-    }
-    if (out_host) stage_d2h(&Lout, host_inplace ? p->stage_in : p->stage_out, ro, out_im_host, p->stream);
-    if (in_host || out_host) fa_hip_stream_sync(p->stream);
-}
-
-/* One execution on the plan's own arrays with a HIP event pair around every
-   launch (on the stream the kernels run on).  ms[i] / launches[i] accumulate
-   the time and the number of launches of step i.  Returns the step count. */
-int fftw_amd_execute_profiled(fftw_plan p, double *ms, long long *launches, int cap) {
-    int i;
-    if (!p || cap < p->nsteps) return -1;
-    for (i = 0; i < p->nsteps; ++i) { ms[i] = 0.0; launches[i] = 0; }
-    pthread_mutex_lock(&p->lock);
-    p->prof_ms = ms;
-    p->prof_launches = launches;
-    fa_run_locked(p, p->ri, p->ii, p->ro, p->io);
-    p->prof_ms = NULL;
-    p->prof_launches = NULL;
-    pthread_mutex_unlock(&p->lock);
-    return p->nsteps;
 }
 
 /* ------------------------------------------------------------- printing */

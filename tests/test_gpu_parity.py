@@ -1154,7 +1154,7 @@ def test_pair_launches_of_the_two_pass_plan(torch_dev, monkeypatch):
 
 @pytest.mark.parametrize("lanes", [2, 3, 4])
 def test_chunk_lanes(torch_dev, monkeypatch, lanes):
-    """chunk lanes (fa_run_locked, round 3): chunk c of a multi-pass plan runs all its steps on stream c % lanes
+    """chunk lanes (run_chunks in fftw3_amd/csrc/exec.c, round 3): chunk c of a multi-pass plan runs all its steps on stream c % lanes
     in scratch slot c % lanes, the lanes overlap freely and join the caller's stream at the end.  Two-pass
     2^20 (ragged last chunk, both signs, in place, new-array execute, a second execution right behind the
     first on the same stream), a three-pass length, r2c with its untangle step, and a 2-D plan whose chunks
@@ -1258,8 +1258,9 @@ def test_new_array_execute_on_less_aligned_arrays_falls_back(torch_dev):
 
 def test_host_arrays_are_staged_chunk_by_chunk(torch_dev):
     """dense batched transforms on plain host arrays that run in several chunks: upload, compute and download
-    of different chunks overlap on separate streams (fa_run_locked, host pipeline).  Ordinary launches (2-pass
-    n = 65536), pair launches (n = 2^20), r2c, ragged last chunk; results against the oracle, input untouched."""
+    of different chunks overlap on separate streams (the host pipeline of host_io in fftw3_amd/csrc/exec.c).  Serial
+    chunks (2-pass n = 65536), two chunk lanes (n = 2^20: the default, so no pair launches here; those are
+    test_host_pipeline_over_pair_launches), r2c, ragged last chunk; results against the oracle, input untouched."""
     rng = np.random.default_rng(99)
     try:
         for n, b, chunk_bytes in ((1 << 16, 11, 2 << 20), (1 << 20, 5, 32 << 20)):
@@ -1285,6 +1286,34 @@ def test_host_arrays_are_staged_chunk_by_chunk(torch_dev):
         assert 1 <= p.chunk < b
         p.execute()
         assert aerror(yr, oracle_r2c(xr, (n,), b).reshape(b, n // 2 + 1)) < TOL
+    finally:
+        fa.set_chunk_bytes(0)
+
+
+def test_host_pipeline_over_pair_launches(torch_dev, monkeypatch):
+    """the host pipeline under pair launches (run_pair in fftw3_amd/csrc/exec.c): one lane, n = 2^20 in chunks of 2 and 1
+    transforms on plain host arrays -- chunk k is waited for before the launch that holds its pass 1 and downloaded
+    after the launch that holds its pass 2.  The pair kernel exists for n = 2^20 only, so this is the smallest
+    shape that gets here.  Results against the oracle, input untouched, then new arrays."""
+    monkeypatch.setenv("FFTW_AMD_LANES", "1")
+    rng = np.random.default_rng(101)
+    n, b = 1 << 20, 3
+    try:
+        fa.set_chunk_bytes(32 << 20)
+        x = crand(rng, b, n)
+        x0 = x.copy()
+        y = np.zeros_like(x)
+        p = fa.plan_many_dft(1, [n], b, x, None, 1, n, y, None, 1, n, fa.FORWARD)
+        assert p.chunk == 2
+        p.execute()
+        assert p.paired
+        assert np.array_equal(x, x0)
+        assert aerror(y, oracle_dft(x, (n,), b).reshape(b, n)) < TOL
+        x2 = crand(rng, b, n)
+        y2 = np.zeros_like(x2)
+        p.execute_dft(x2, y2)
+        assert p.paired
+        assert aerror(y2, oracle_dft(x2, (n,), b).reshape(b, n)) < TOL
     finally:
         fa.set_chunk_bytes(0)
 
