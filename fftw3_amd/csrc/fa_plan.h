@@ -71,6 +71,8 @@ typedef struct {
     int real_img;         /* FFTW_AMD_REAL_IMG: batches of small 2-D r2c / c2r transforms in one trip (emit_real_image,
                              FFTW_AMD_K_IMG2DR) instead of the three-trip plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
                              candidate */
+    int vol3d;            /* FFTW_AMD_VOL3D: batches of small 3-D c2c transforms in one trip (emit_vol3d, FFTW_AMD_K_VOL3D)
+                             instead of one trip per axis; off under FFTW_ESTIMATE, a FFTW_MEASURE candidate */
 } fa_cfg;
 
 typedef struct {

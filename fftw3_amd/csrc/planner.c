@@ -58,6 +58,7 @@ fa_cfg fa_default_cfg(void) {
     c.tile_elems = 0;
     c.real_dec = 0;
     c.real_img = 0;
+    c.vol3d = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -75,6 +76,8 @@ fa_cfg fa_default_cfg(void) {
     if (e) c.real_dec = atoi(e) != 0;
     e = getenv("FFTW_AMD_REAL_IMG");
     if (e) c.real_img = atoi(e) != 0;
+    e = getenv("FFTW_AMD_VOL3D");
+    if (e) c.vol3d = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
@@ -1375,6 +1378,52 @@ static int emit_img2dl(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     return emit_images(p, in, out, sw_in, sw_out, FFTW_AMD_K_IMG2DL);
 }
 
+/* A batch of small three-dimensional transforms n0 x n1 x n2 on dense contiguous volumes, in ONE trip
+   (FFTW_AMD_K_VOL3D, pass3d.hpp): a workgroup takes T whole volumes and does all three axes in registers, where the
+   axis-by-axis plan crosses HBM three times.  The step has no other executor, so everything it needs is settled here:
+   rank 3, interleaved arrays, dense rows, planes and volumes, at most one howmany loop that steps over exactly one
+   volume on both sides, 16-byte aligned arrays, no FFTW_UNALIGNED.  No scratch, no tables, in place or out of place.
+   fa_hip_vol3d_tile is the only source of what the kernel covers.  Off under FFTW_ESTIMATE (cfg.vol3d,
+   FFTW_AMD_VOL3D=1): the numpy step interpreter of the CPU tier does not know the step, so it stays an opt-in and a
+   FFTW_MEASURE candidate until that interpreter learns it.  FFTW_AMD_NO_IMG2D=1 and FFTW_AMD_NO_TUNED=1 switch it off
+   like the image steps.  1 = emitted. */
+static int emit_vol3d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    const fa_dim *d0 = &p->dims[0], *d1 = &p->dims[1], *d2 = &p->dims[2];
+    fftw_amd_step_desc *s;
+    sdim d;
+    i64 n0, n1, n2, vol;
+    int T;
+    if (!p->cfg.vol3d || p->rank != 3 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    n0 = d0->n; n1 = d1->n; n2 = d2->n;
+    if (n0 > 32 || n1 > 32 || n2 > 32) return 0;
+    T = fa_hip_vol3d_tile((int)n0, (int)n1, (int)n2);
+    if (T <= 0) return 0;
+    vol = 2 * n0 * n1 * n2;
+    if (in.im != 1 || out.im != 1) return 0;
+    if (d2->is != 2 || d2->os != 2 || d1->is != 2 * n2 || d1->os != 2 * n2 || d0->is != 2 * n1 * n2 || d0->os != 2 * n1 * n2) return 0;
+    if (p->hrank && (p->hdims[0].is != vol || p->hdims[0].os != vol)) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    s = new_step(p, FFTW_AMD_STEP_PASS);
+    step_set_locs(s, in, out);
+    s->flags = sw_in | sw_out | FFTW_AMD_F_LO_DFT | FFTW_AMD_F_VOL3D;
+    s->L = (int)n2;
+    s->is_l = 2;
+    s->os_l = 2;
+    s->nradices = fa_radices(n2, s->radices);
+    if (s->nradices < 0) { p->failed = 1; return 1; }
+    s->tile_lo_n = (int)n1;
+    s->tile_lo_is = 2 * n2;
+    s->tile_lo_os = 2 * n2;
+    s->aux_n = n0;
+    d.n = p->hrank ? p->chunk : 1; d.is = vol; d.os = vol; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
+    step_set_dims(p, s, &d, 1, 0);
+    s->tile = T;
+    s->variant = FFTW_AMD_K_VOL3D;
+    p->est_flops += 5.0 * (double)(n0 * n1 * n2) * (double)d.n * log2((double)(n0 * n1 * n2));
+    return 1;
+}
+
 static void build_c2c_on(plan *p, fa_loc in, fa_loc out);
 
 /* One copy src -> dst over ALL dims of the problem as loops (transform dims, then the howmany dims of the current
@@ -1486,6 +1535,7 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
     if (emit_rows_lo_dft(p, in, out, sw_in, sw_out)) return;
     if (emit_img2d(p, in, out, sw_in, sw_out)) return;
     if (emit_img2dl(p, in, out, sw_in, sw_out)) return;
+    if (emit_vol3d(p, in, out, sw_in, sw_out)) return;
     for (a = p->rank - 1; a >= 0; --a) {
         fa_axis ax;
         memset(&ax, 0, sizeof(ax));
@@ -2582,6 +2632,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DR) sapp(s, cap, &len, "img2d-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_VOL3D) sapp(s, cap, &len, "vol3d-%dx%dx%d", (int)d->aux_n, d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);
             else {
                 sapp(s, cap, &len, "lds:");

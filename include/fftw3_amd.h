@@ -347,8 +347,10 @@ enum {
                                    intra-axis twiddles are the stage tables `table` (row axis, L entries) and `table2` (column
                                    axis, tile_lo_n entries), -1 for an axis of one stage; tw_n = 0.  The plan owns these tables, so
                                    fftw_amd_plan_workspace_bytes is 16 bytes per entry of them; it owns no scratch buffer */
-    FFTW_AMD_K_IMG2DR = 11      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole small REAL images in one trip, r2c or c2r
+    FFTW_AMD_K_IMG2DR = 11,     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole small REAL images in one trip, r2c or c2r
                                    (pass2dr.hpp); see the flag for the fields.  No fallback executor */
+    FFTW_AMD_K_VOL3D = 12       /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT and FFTW_AMD_F_VOL3D: whole small volumes in one trip
+                                   (pass3d.hpp); see FFTW_AMD_F_VOL3D for the fields.  No fallback executor */
 };
 
 enum {
@@ -401,6 +403,16 @@ enum {
                                       With pitch = n1 + 2 an image occupies the same words on both sides and the step may run
                                       in place: every word of an image is read before any is written.  The padding words of
                                       padded real rows are never written.  Planned only for aligned arrays */
+    FFTW_AMD_F_VOL3D     = 1 << 19,/* pass of variant FFTW_AMD_K_VOL3D (always with FFTW_AMD_F_LO_DFT): the step is the 3-D DFT
+                                      aux_n x tile_lo_n x L of dense row-major interleaved volumes n0 x n1 x n2, every extent at
+                                      most 32 and at most 8192 points: L = n2 (is_l = os_l = 2), tile_lo_n = n1 (rows
+                                      tile_lo_is = tile_lo_os = 2 n2 doubles apart), aux_n = n0 (planes 2 n1 n2 doubles apart),
+                                      Y[k0][k1][k2] = sum x[j0][j1][j2] w_n0^(j0 k0) w_n1^(j1 k1) w_n2^(j2 k2).
+                                      dims[0] is the loop over the volumes of the chunk (strides 2 n0 n1 n2 on both sides),
+                                      tile = volumes per workgroup, tw_n = 0, table = table2 = -1, src_im = dst_im = 1.
+                                      Backward transforms carry FFTW_AMD_F_SWAP_IN and _SWAP_OUT, both or neither.  Every word
+                                      of a volume is read before any is written, so the step may run in place.  No fallback
+                                      executor: planned only for aligned interleaved arrays */
     FFTW_AMD_F_REAL_DEC_C2R = 1 << 17 /* pass: the FIRST trip of a two-trip c2r transform of n = L1 x L real points (pass3t_kernel,
                                       RD = 2), the backward twin of FFTW_AMD_F_REAL_DEC.  The source is the half spectrum
                                       X[0 ... n / 2], entry k at k1 dim_is[0] + k2 is_l for k = k1 + L1 k2 (so is_l = L1 dim_is[0]).
