@@ -62,10 +62,12 @@ F_REAL_DEC = 1 << 15
 F_REAL_DEC_C2R = 1 << 17
 F_REAL_IMG = 1 << 18
 F_VOL3D = 1 << 19
+F_REAL_VOL = 1 << 20
 F_PAIR_SWAP = 1 << 16
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
 K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL, K_IMG2DR = range(12)
 K_VOL3D = 12
+K_VOL3DR = 13
 
 
 class StepDesc(C.Structure):
@@ -230,6 +232,8 @@ _sig("fa_hip_img2dl_tile", C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_img2dr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_lds", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int))
+_sig("fa_hip_vol3dr_tile", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
+_sig("fa_hip_vol3dr_lds", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int))
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [_vp]
 
@@ -267,6 +271,12 @@ def vol3d_tile(n0, n1, n2):
     """volumes per workgroup of the one-trip small-volume kernel (pass3d.hpp, vol3d_menu.inc) for row-major volumes
     n0 x n1 x n2; 0: the kernel does not cover that size.  Needs no device"""
     return int(lib.fa_hip_vol3d_tile(n0, n1, n2))
+
+
+def vol3dr_tile(n0, n1, n2, fwd=True):
+    """volumes per workgroup of the one-trip real-volume kernels (pass3dr.hpp, vol3dr_menu.inc) for row-major volumes of
+    n0 x n1 x n2 reals, r2c (fwd) or c2r; 0: the kernels do not cover that size.  Needs no device"""
+    return int(lib.fa_hip_vol3dr_tile(n0, n1, n2, 1 if fwd else 0))
 
 
 def elem_form(step, src_mis, dst_mis, cn):

@@ -31,6 +31,8 @@ int   fa_hip_img2d_tile(int n0, int n1);  /* images per tile of the one-trip sma
 int   fa_hip_img2dl_tile(int n0, int n1); /* the same for the kernel of extents above 32 (img2dl_menu.inc), 0: none */
 int   fa_hip_img2dr_tile(int n0, int n1, int fwd); /* ... of the small real-image kernels, r2c (fwd) or c2r (img2dr_menu.inc), 0: none */
 int   fa_hip_vol3d_tile(int n0, int n1, int n2);   /* volumes per tile of the one-trip small-volume kernel (vol3d_menu.inc), 0: none */
+int   fa_hip_vol3dr_tile(int n0, int n1, int n2, int fwd); /* ... of the small real-volume kernels, r2c (fwd) or c2r (vol3dr_menu.inc), 0: none */
+int   fa_hip_vol3dr_lds(int n0, int n1, int n2, int fwd, int *st); /* their LDS bytes; st[0 ... 3]: row and plane stride of the two layouts (pass3dr.hpp), 0: none */
 int   fa_hip_vol3d_lds(int n0, int n1, int n2, int *s, int *sp); /* its LDS bytes, row and plane stride in doubles (pass3d.hpp), 0: none */
 /* The kernel form that an element-wise step takes (kernels_elem.hip) for a batch chunk of cn transforms whose
    source / destination addresses are src_mis / dst_mis bytes past a 16-byte boundary.  Needs no device. */

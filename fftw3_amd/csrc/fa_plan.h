@@ -73,6 +73,9 @@ typedef struct {
                              candidate */
     int vol3d;            /* FFTW_AMD_VOL3D: batches of small 3-D c2c transforms in one trip (emit_vol3d, FFTW_AMD_K_VOL3D)
                              instead of one trip per axis; off under FFTW_ESTIMATE, a FFTW_MEASURE candidate */
+    int real_vol;         /* FFTW_AMD_REAL_VOL: batches of small 3-D r2c / c2r transforms in one trip (emit_real_volume,
+                             FFTW_AMD_K_VOL3DR) instead of the axis-by-axis plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
+                             candidate; a knob of its own, not implied by real_img */
 } fa_cfg;
 
 typedef struct {

@@ -502,6 +502,12 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
         fprintf(stderr, "fftw3_amd: internal error: small-volume step %d x %d x %d with an unsupported layout\n", (int)d->aux_n, d->tile_lo_n, d->L);
         return -1;
     }
+    if (d->variant == FFTW_AMD_K_VOL3DR) {
+        /* whole small real volumes, r2c or c2r (kernels_volr.hip) */
+        if (fa_launch_vol3dr(d, bufs, tables, cs, cn, st) == 0) return 0;
+        fprintf(stderr, "fftw3_amd: internal error: real-volume step %d x %d x %d with an unsupported layout\n", (int)d->aux_n, d->tile_lo_n, d->L);
+        return -1;
+    }
     if (d->variant == FFTW_AMD_K_P1024 && launch_p1024(d, bufs, tables, cs, cn, st) == 0) return 0;
     if (d->variant == FFTW_AMD_K_BLUE) return fa_launch_blue(d, bufs, tables, cs, cn, st);
     if (d->variant == FFTW_AMD_K_R1 && fa_launch_pass1r(d, bufs, tables, cs, cn, st) == 0) return 0;

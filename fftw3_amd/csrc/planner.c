@@ -59,6 +59,7 @@ fa_cfg fa_default_cfg(void) {
     c.real_dec = 0;
     c.real_img = 0;
     c.vol3d = 0;
+    c.real_vol = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -78,6 +79,8 @@ fa_cfg fa_default_cfg(void) {
     if (e) c.real_img = atoi(e) != 0;
     e = getenv("FFTW_AMD_VOL3D");
     if (e) c.vol3d = atoi(e) != 0;
+    e = getenv("FFTW_AMD_REAL_VOL");
+    if (e) c.real_vol = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
@@ -1985,6 +1988,61 @@ static int emit_real_image(plan *p, int fwd) {
     return 1;
 }
 
+/* A batch of small three-dimensional r2c (fwd) or c2r transforms n0 x n1 x n2 in ONE trip (FFTW_AMD_K_VOL3DR,
+   pass3dr.hpp): a workgroup takes T whole real volumes and does all three axes in registers, where the axis-by-axis
+   plans make one trip for the real axis, one for the untangle / tangle and one per complex axis, through a scratch
+   buffer.  The step has no other executor, so everything it needs is settled here: rank 3, at most one howmany loop
+   that steps over exactly one volume on both sides, the real side with element stride 1, row pitch n2 or n2 + 2, plane
+   pitch n1 rows and volume pitch n0 planes, the complex side interleaved with stride 2, rows of n2 / 2 + 1 entries
+   and dense planes and volumes, 16-byte aligned arrays, no FFTW_UNALIGNED.  In place only with the padded pitch (a
+   volume then occupies the same words on both sides).  No scratch, no table.  fa_hip_vol3dr_tile is the only source
+   of what the kernels cover.  Off under FFTW_ESTIMATE (cfg.real_vol, FFTW_AMD_REAL_VOL=1 -- a knob of its own:
+   existing tests plan rank-3 real problems with FFTW_AMD_REAL_IMG=1 and interpret them with the base numpy
+   interpreter, which does not know the step); a candidate of the FFTW_MEASURE search for rank-3 r2c / c2r problems,
+   remembered by wisdom.  FFTW_AMD_NO_IMG2D=1 and FFTW_AMD_NO_TUNED=1 switch it off like its siblings.  1 = emitted. */
+static int emit_real_volume(plan *p, int fwd) {
+    const fa_dim *d0 = &p->dims[0], *d1 = &p->dims[1], *d2 = &p->dims[2];
+    fftw_amd_step_desc *s;
+    fa_loc in = { 0, 0, fwd ? 0 : p->in_im }, out = { 1, 0, fwd ? p->out_im : 0 };
+    sdim d;
+    i64 n0, n1, n2, cp, rp, r_vol, c_vol;
+    int T;
+    if (!p->cfg.real_vol || p->rank != 3 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    n0 = d0->n; n1 = d1->n; n2 = d2->n;
+    if (n0 > 32 || n1 > 32 || n2 > 32) return 0;
+    T = fa_hip_vol3dr_tile((int)n0, (int)n1, (int)n2, fwd);
+    if (T <= 0) return 0;
+    cp = n2 + 2;
+    rp = fwd ? d1->is : d1->os;
+    if ((fwd ? p->out_im : p->in_im) != 1) return 0;
+    if ((fwd ? d2->is : d2->os) != 1 || (fwd ? d2->os : d2->is) != 2) return 0;
+    if ((rp != n2 && rp != cp) || (fwd ? d1->os : d1->is) != cp) return 0;
+    if ((fwd ? d0->is : d0->os) != n1 * rp || (fwd ? d0->os : d0->is) != n1 * cp) return 0;
+    r_vol = n0 * n1 * rp; c_vol = n0 * n1 * cp;
+    if (p->hrank && ((fwd ? p->hdims[0].is : p->hdims[0].os) != r_vol || (fwd ? p->hdims[0].os : p->hdims[0].is) != c_vol)) return 0;
+    if (p->inplace && rp != cp) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    s = new_step(p, FFTW_AMD_STEP_PASS);
+    step_set_locs(s, in, out);
+    s->flags = FFTW_AMD_F_REAL_VOL | (fwd ? FFTW_AMD_F_REAL_IN : FFTW_AMD_F_REAL_OUT);
+    s->L = (int)n2;
+    s->is_l = fwd ? 1 : 2;
+    s->os_l = fwd ? 2 : 1;
+    s->nradices = fa_radices(n2, s->radices);
+    if (s->nradices < 0) { p->failed = 1; return 1; }
+    s->tile_lo_n = (int)n1;
+    s->tile_lo_is = fwd ? rp : cp;
+    s->tile_lo_os = fwd ? cp : rp;
+    s->aux_n = n0;
+    d.n = p->hrank ? p->chunk : 1; d.is = fwd ? r_vol : c_vol; d.os = fwd ? c_vol : r_vol; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
+    step_set_dims(p, s, &d, 1, 0);
+    s->tile = T;
+    s->variant = FFTW_AMD_K_VOL3DR;
+    p->est_flops += 2.5 * (double)(n0 * n1 * n2) * (double)d.n * log2((double)(n0 * n1 * n2));
+    return 1;
+}
+
 /* r2c: last dim real -> half spectrum, then complex DFTs over the other dims
    on the half-spectrum array (reference rank_geq2_rdft2 A.c:10111-10282).
    p->dims[].is are strides of the REAL array (doubles), .os of the complex
@@ -1996,6 +2054,7 @@ static void build_r2c(plan *p) {
     fa_loc in = { 0, 0, 0 }, out = { 1, 0, p->out_im };
     fa_axis ax;
     if (emit_real_image(p, 1)) return;
+    if (emit_real_volume(p, 1)) return;
     for (j = 0; j < r; ++j) ext[j] = p->dims[j].n;
     ext[r - 1] = half;
 
@@ -2175,6 +2234,7 @@ static void build_c2r(plan *p) {
     fa_axis ax;
 
     if (emit_real_image(p, 0)) return;
+    if (emit_real_volume(p, 0)) return;
     for (j = 0; j < r; ++j) { ext[j] = p->dims[j].n; cdims[j] = p->dims[j]; cdims[j].os = p->dims[j].is; }
     ext[r - 1] = half;
     for (j = 0; j < p->hrank; ++j) { chd[j] = p->hdims[j]; chd[j].os = p->hdims[j].is; }
@@ -2632,6 +2692,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DR) sapp(s, cap, &len, "img2d-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_VOL3DR) sapp(s, cap, &len, "vol3d-%s-%dx%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", (int)d->aux_n, d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_VOL3D) sapp(s, cap, &len, "vol3d-%dx%dx%d", (int)d->aux_n, d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);
             else {

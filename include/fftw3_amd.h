@@ -349,8 +349,10 @@ enum {
                                    fftw_amd_plan_workspace_bytes is 16 bytes per entry of them; it owns no scratch buffer */
     FFTW_AMD_K_IMG2DR = 11,     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole small REAL images in one trip, r2c or c2r
                                    (pass2dr.hpp); see the flag for the fields.  No fallback executor */
-    FFTW_AMD_K_VOL3D = 12       /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT and FFTW_AMD_F_VOL3D: whole small volumes in one trip
+    FFTW_AMD_K_VOL3D = 12,      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT and FFTW_AMD_F_VOL3D: whole small volumes in one trip
                                    (pass3d.hpp); see FFTW_AMD_F_VOL3D for the fields.  No fallback executor */
+    FFTW_AMD_K_VOL3DR = 13      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_VOL: whole small REAL volumes in one trip, r2c or c2r
+                                   (pass3dr.hpp); see the flag for the fields.  No fallback executor */
 };
 
 enum {
@@ -413,6 +415,26 @@ enum {
                                       Backward transforms carry FFTW_AMD_F_SWAP_IN and _SWAP_OUT, both or neither.  Every word
                                       of a volume is read before any is written, so the step may run in place.  No fallback
                                       executor: planned only for aligned interleaved arrays */
+    FFTW_AMD_F_REAL_VOL  = 1 << 20,/* pass of variant FFTW_AMD_K_VOL3DR: the whole 3-D r2c (with FFTW_AMD_F_REAL_IN) or c2r (with
+                                      FFTW_AMD_F_REAL_OUT) transform of real row-major volumes of aux_n = n0 planes x tile_lo_n =
+                                      n1 rows x L = n2 real columns, n2 even, every extent at most 32.  dims[0] is the loop over
+                                      the volumes of the chunk, tile = volumes per workgroup, tw_n = 0, table = table2 = -1, no
+                                      swap flags, neither FFTW_AMD_F_LO_DFT nor FFTW_AMD_F_VOL3D.  The complex side is the dense
+                                      half spectrum: n0 x n1 rows of n2 / 2 + 1 interleaved entries (im = 1, entries 2 apart,
+                                      rows n2 + 2 doubles apart, planes n1 (n2 + 2) apart, volumes n0 n1 (n2 + 2) apart); the
+                                      real side has im = 0, elements 1 apart, rows `pitch` = n2 or n2 + 2 doubles apart, planes
+                                      n1 pitch apart and volumes n0 n1 pitch apart.
+                                      r2c: src_im = 0, is_l = 1, tile_lo_is = pitch, dim_is[0] = n0 n1 pitch; dst_im = 1,
+                                      os_l = 2, tile_lo_os = n2 + 2, dim_os[0] = n0 n1 (n2 + 2);
+                                      Y[k0][k1][k2] = sum x[j0][j1][j2] w_n0^(j0 k0) w_n1^(j1 k1) w_n2^(j2 k2), k2 = 0 ... n2 / 2.
+                                      c2r: the same fields with the sides exchanged (src_im = 1, is_l = 2, tile_lo_is = n2 + 2,
+                                      dst_im = 0, os_l = 1, tile_lo_os = pitch).  First the backward DFTs of length n0 and n1
+                                      over the two leading axes for each of the n2 / 2 + 1 columns, then the 1-D c2r of length
+                                      n2 along each row, which reads the imaginary parts of its entries 0 and n2 / 2 as 0 (half
+                                      spectra need not be Hermitian).
+                                      With pitch = n2 + 2 a volume occupies the same words on both sides and the step may run
+                                      in place: every word of a volume is read before any is written.  The padding words of
+                                      padded real rows are never written.  Planned only for aligned arrays */
     FFTW_AMD_F_REAL_DEC_C2R = 1 << 17 /* pass: the FIRST trip of a two-trip c2r transform of n = L1 x L real points (pass3t_kernel,
                                       RD = 2), the backward twin of FFTW_AMD_F_REAL_DEC.  The source is the half spectrum
                                       X[0 ... n / 2], entry k at k1 dim_is[0] + k2 is_l for k = k1 + L1 k2 (so is_l = L1 dim_is[0]).
