@@ -383,11 +383,19 @@ static void io_end(plan *p, host_io *h) {
 
 /* ---------------------------------------------------------------- schedules */
 
-/* step i with the re/im distances of this call: split-array callers may pass different ones per call */
+/* step i with the re/im distances of this call: split-array callers may pass different ones per call, and staged host
+   planes lie at a distance of their own.  Both ends of a step count: a plan of rank >= 2 runs its later axes in place on
+   the output array (buf1 -> buf1), a c2r plan may run its leading axes in place on the input (buf0 -> buf0). */
 static fftw_amd_step_desc step_for_call(const plan *p, int i, i64 in_im, i64 out_im) {
     fftw_amd_step_desc d = p->steps[i];
-    if (d.src_buf == 0 && !FA_REAL_IN(p->type) && d.src_im == p->in_im) d.src_im = in_im;
-    if (d.dst_buf == 1 && !FA_REAL_OUT(p->type) && d.dst_im == p->out_im) d.dst_im = out_im;
+    if (!FA_REAL_IN(p->type)) {
+        if (d.src_buf == 0 && d.src_im == p->in_im) d.src_im = in_im;
+        if (d.dst_buf == 0 && d.dst_im == p->in_im) d.dst_im = in_im;
+    }
+    if (!FA_REAL_OUT(p->type)) {
+        if (d.src_buf == 1 && d.src_im == p->out_im) d.src_im = out_im;
+        if (d.dst_buf == 1 && d.dst_im == p->out_im) d.dst_im = out_im;
+    }
     return d;
 }
 

@@ -6,7 +6,9 @@ element holds 0x7ff8_0000_0000_0000 | word index: a stray write shows as a chang
 another guard word), a used over-read of a gap shows as a NaN in the result, and the input of an out-of-place plan
 must come back bit for bit.  footprint() is written from the API definition (fftw3 manual, "Advanced Complex DFTs",
 "Advanced Real-data DFTs", "Guru vector and transform sizes") with numpy index arithmetic, never from a plan's
-steps.  Nothing here needs a GPU except Arena.to_device().
+steps: a layout is the guru interface's list of (n, is, os) per dimension plus the howmany dims, and the embed /
+stride / dist form of the advanced interface is one constructor of that list (embed_dims).  Nothing here needs a GPU
+except Arena.to_device().
 
 Problem describes one plan (transform, both layouts, in place / split / host / flags), builds its arenas, scatters
 the logical input, makes the plan on whatever arrays it is given and gathers the logical output; the CPU tier
@@ -19,7 +21,7 @@ NAN_BASE = 0x7FF8000000000000
 GUARD_MIN = 8192          # doubles: 64 KiB
 GUARD_ROUND = 512         # doubles: 4 KiB, so that the payload keeps the alignment of a bare allocation
 KINDS = ("c2c", "r2c", "c2r", "r2r")
-SIDES = ("complex", "split", "real", "halfcomplex", "r2r")
+SIDES = ("complex", "split", "real", "halfcomplex", "split-halfcomplex", "r2r")
 
 
 def _round_up(v, m):
@@ -87,27 +89,51 @@ def colocate(arenas):
 
 def logical_shape(n, side):
     n = tuple(int(v) for v in n)
-    if side == "halfcomplex":
+    if side.endswith("halfcomplex"):
         return n[:-1] + (n[-1] // 2 + 1,)
     return n
 
 
-def elem_offsets(shape, howmany, embed, stride, dist):
-    """element offsets (in elements of the side's type) of `howmany` row-major sub-arrays `shape` of arrays `embed`:
-    element (b, j0, ..., jr) sits at b dist + stride (... (j0 embed1 + j1) embed2 + ...); shape (howmany,) + shape"""
+def embed_strides(shape, embed, stride):
+    """per-dimension strides of a row-major sub-array `shape` of an array `embed` whose elements are `stride` apart:
+    element (j0, ..., jr) sits at stride (... (j0 embed1 + j1) embed2 + ...)"""
     shape = tuple(int(v) for v in shape)
     embed = shape if embed is None else tuple(int(v) for v in embed)
     assert len(embed) == len(shape) and all(e >= s for e, s in zip(embed[1:], shape[1:]))
-    r = len(shape)
-    off = np.zeros((1,) * (r + 1), dtype=np.int64)
-    mult = 1
-    for ax in range(r - 1, -1, -1):
-        sh = [1] * (r + 1)
-        sh[ax + 1] = shape[ax]
-        off = off + np.arange(shape[ax], dtype=np.int64).reshape(sh) * mult
+    out, mult = [], int(stride)
+    for ax in range(len(shape) - 1, -1, -1):
+        out.insert(0, mult)
         mult *= embed[ax]
-    b = np.arange(howmany, dtype=np.int64).reshape((howmany,) + (1,) * r)
-    return b * int(dist) + off * int(stride)
+    return out
+
+
+def embed_dims(n, howmany, inembed, istride, idist, onembed, ostride, odist, in_side, out_side):
+    """the advanced interface's embed / stride / dist as the guru interface's (dims, howmany dims): lists of
+    (n, is, os), the strides in elements of each side's type"""
+    si = embed_strides(logical_shape(n, in_side), inembed, istride)
+    so = embed_strides(logical_shape(n, out_side), onembed, ostride)
+    return ([(int(v), a, b) for v, a, b in zip(n, si, so)], [(int(howmany), int(idist), int(odist))])
+
+
+def elem_offsets(dims, hdims):
+    """element offsets of the vector of transforms that the guru lists describe for one side: dims is [(n, stride)]
+    per dimension (n in the side's elements), hdims [(n, stride)] per howmany dimension, the first the slowest.
+    Shape (product of the howmany extents,) + (n per dimension)"""
+    r, h = len(dims), len(hdims)
+    off = np.zeros((1,) * (h + r), dtype=np.int64)
+    for ax, (n, st) in enumerate(list(hdims) + list(dims)):
+        sh = [1] * (h + r)
+        sh[ax] = int(n)
+        off = off + np.arange(int(n), dtype=np.int64).reshape(sh) * int(st)
+    hm = int(np.prod([n for n, _ in hdims], dtype=np.int64)) if h else 1
+    return off.reshape((hm,) + tuple(int(n) for n, _ in dims))
+
+
+def side_dims(dims, hdims, side, which):
+    """one side of guru lists of (n, is, os): [(n, stride)] with the last extent halved on a half-complex side"""
+    k = 1 if which == "in" else 2
+    shape = logical_shape([d[0] for d in dims], side)
+    return [(n, d[k]) for n, d in zip(shape, dims)], [(d[0], d[k]) for d in hdims]
 
 
 def word_offsets(elems, side):
@@ -117,12 +143,13 @@ def word_offsets(elems, side):
     return elems[..., None]
 
 
-def footprint(kind, rank, n, howmany, embed, stride, dist, side):
-    """sorted word offsets, from the pointer given to the planner, that the layout's definition says are read (an
-    input side) or written (an output side).  side: "complex" (interleaved), "split" (one plane; both planes have
-    the same set), "real", "halfcomplex" (n_last / 2 + 1 interleaved elements in the last dimension) or "r2r"."""
-    assert kind in KINDS and side in SIDES and rank == len(n)
-    w = word_offsets(elem_offsets(logical_shape(n, side), howmany, embed, stride, dist), side)
+def footprint(kind, dims, hdims, side, which):
+    """sorted word offsets, from the pointer given to the planner, that the layout's definition says are read
+    (which = "in") or written ("out"); dims, hdims: the guru lists of (n, is, os).  side: "complex" (interleaved),
+    "split" / "split-halfcomplex" (one plane; both planes have the same set), "real", "halfcomplex" (n_last / 2 + 1
+    interleaved elements in the last dimension) or "r2r"."""
+    assert kind in KINDS and side in SIDES and which in ("in", "out")
+    w = word_offsets(elem_offsets(*side_dims(dims, hdims, side, which)), side)
     w = w.reshape(-1)
     return w if np.all(w[1:] > w[:-1]) else np.unique(w)
 
@@ -183,9 +210,20 @@ class Layout(object):
         self.stride, self.dist = int(stride), dist
 
 
+class Guru(object):
+    """one side of a guru call, where embed / stride / dist cannot say it: the stride of every dimension and the
+    howmany dims [(n, stride), ...], the first the slowest, in the side's elements (reals on a split side)"""
+
+    def __init__(self, strides, hdims):
+        self.strides = [int(v) for v in strides]
+        self.hdims = [(int(n), int(d)) for n, d in hdims]
+
+
 class Problem(object):
-    """kind, shape, howmany, both layouts; inplace: one shared array; split: separate real / imaginary planes
-    (c2c, rank 1, through the guru interface, strides then count reals); r2r: the kinds, one per dimension"""
+    """kind, shape, howmany, both layouts; inplace: one shared array; split: the complex sides (both of c2c, the
+    output of r2c, the input of c2r) are separate real / imaginary planes whose strides count reals; r2r: the
+    kinds, one per dimension.  A Problem with a split or a Guru side is planned through the guru interface, every
+    other through plan_many_*"""
 
     def __init__(self, kind, shape, hm, lin, lout, sign=-1, r2r=None, inplace=False, split=False, flags=0, offset=0):
         self.kind, self.shape, self.hm, self.sign = kind, tuple(int(v) for v in shape), int(hm), sign
@@ -194,17 +232,28 @@ class Problem(object):
         self.in_side = {"c2c": "complex", "r2c": "real", "c2r": "halfcomplex", "r2r": "r2r"}[kind]
         self.out_side = {"c2c": "complex", "r2c": "halfcomplex", "c2r": "real", "r2r": "r2r"}[kind]
         if split:
-            assert kind == "c2c" and len(self.shape) == 1
-            self.in_side = self.out_side = "split"
-        self.lin, self.lout = self._full(lin, self.in_side), self._full(lout, self.out_side)
-        r = len(self.shape)
-        self.in_elems = elem_offsets(logical_shape(self.shape, self.in_side), hm, self.lin.embed, self.lin.stride,
-                                     self.lin.dist)
-        self.out_elems = elem_offsets(logical_shape(self.shape, self.out_side), hm, self.lout.embed, self.lout.stride,
-                                      self.lout.dist)
-        self.in_fp = footprint(kind, r, self.shape, hm, self.lin.embed, self.lin.stride, self.lin.dist, self.in_side)
-        self.out_fp = footprint(kind, r, self.shape, hm, self.lout.embed, self.lout.stride, self.lout.dist,
-                                self.out_side)
+            assert kind in ("c2c", "r2c", "c2r") and not (inplace and kind != "c2c")
+            to_split = {"complex": "split", "halfcomplex": "split-halfcomplex"}
+            self.in_side, self.out_side = to_split.get(self.in_side, self.in_side), to_split.get(self.out_side,
+                                                                                                 self.out_side)
+        self.nin = 2 if self.in_side.startswith("split") else 1
+        self.guru = split or isinstance(lin, Guru) or isinstance(lout, Guru)
+        if self.guru:
+            gi, go = self._guru(lin, self.in_side), self._guru(lout, self.out_side)
+            assert [n for n, _ in gi.hdims] == [n for n, _ in go.hdims]
+            assert int(np.prod([n for n, _ in gi.hdims], dtype=np.int64)) == self.hm
+            self.lin = self.lout = None
+            self.dims = [(n, a, b) for n, a, b in zip(self.shape, gi.strides, go.strides)]
+            self.hdims = [(n, a, b) for (n, a), (_, b) in zip(gi.hdims, go.hdims)]
+        else:
+            self.lin, self.lout = self._full(lin, self.in_side), self._full(lout, self.out_side)
+            li, lo = self.lin, self.lout
+            self.dims, self.hdims = embed_dims(self.shape, hm, li.embed, li.stride, li.dist, lo.embed, lo.stride,
+                                               lo.dist, self.in_side, self.out_side)
+        self.in_elems = elem_offsets(*side_dims(self.dims, self.hdims, self.in_side, "in"))
+        self.out_elems = elem_offsets(*side_dims(self.dims, self.hdims, self.out_side, "out"))
+        self.in_fp = footprint(kind, self.dims, self.hdims, self.in_side, "in")
+        self.out_fp = footprint(kind, self.dims, self.hdims, self.out_side, "out")
 
     def _full(self, lay, side):
         lay = lay or Layout()
@@ -213,39 +262,46 @@ class Problem(object):
         dist = int(np.prod(embed)) * lay.stride if lay.dist is None else int(lay.dist)
         return Layout(embed, lay.stride, dist)
 
+    def _guru(self, lay, side):
+        if isinstance(lay, Guru):
+            return lay
+        lay = self._full(lay, side)
+        return Guru(embed_strides(logical_shape(self.shape, side), lay.embed, lay.stride), [(self.hm, lay.dist)])
+
     # -- arenas
-    def _one_span(self, lay, side):
+    def _one_span(self, side, which):
         """words one transform spans on a side"""
-        e = elem_offsets(logical_shape(self.shape, side), 1, lay.embed, lay.stride, lay.dist)
+        e = elem_offsets(side_dims(self.dims, [], side, which)[0], [])
         return int(word_offsets(e, side).max()) + 1
 
     def arenas(self):
         """the arenas, filled with the NaN pattern: [in, out], [shared] in place, and with split planes
-        [re_in, im_in, re_out, im_out] or [re, im]"""
+        [re_in, im_in, re_out, im_out] (c2c), [in, re_out, im_out] (r2c), [re_in, im_in, out] (c2r) or [re, im]"""
         span_i, span_o = int(self.in_fp.max()) + 1, int(self.out_fp.max()) + 1
-        gi, go = self._one_span(self.lin, self.in_side), self._one_span(self.lout, self.out_side)
+        gi, go = self._one_span(self.in_side, "in"), self._one_span(self.out_side, "out")
         if self.inplace:
             A = [Arena(max(span_i, span_o), np.float64, max(gi, go), self.offset)]
             if self.split:
                 A.append(Arena(max(span_i, span_o), np.float64, max(gi, go)))
             return A
-        A = [Arena(span_i, np.float64, gi, self.offset), Arena(span_o, np.float64, go, self.offset)]
-        if self.split:
-            A = [A[0], Arena(span_i, np.float64, gi), A[1], Arena(span_o, np.float64, go)]
+        A = [Arena(span_i, np.float64, gi, self.offset)]
+        if self.in_side.startswith("split"):
+            A.append(Arena(span_i, np.float64, gi))
+        A.append(Arena(span_o, np.float64, go, self.offset))
+        if self.out_side.startswith("split"):
+            A.append(Arena(span_o, np.float64, go))
         return A
 
     def in_arenas(self, A):
-        return A[:2] if self.split else A[:1]
+        return A[:self.nin]
 
     def out_arenas(self, A):
-        if self.inplace:
-            return A
-        return A[2:] if self.split else A[1:]
+        return A if self.inplace else A[self.nin:]
 
     def scatter(self, A, x):
         """the logical input x, (hm,) + logical input shape, into the input arenas"""
         x = np.asarray(x).reshape(self.in_elems.shape)
-        if self.split:
+        if self.in_side.startswith("split"):
             A[0].put(self.in_elems.reshape(-1), x.real.reshape(-1))
             A[1].put(self.in_elems.reshape(-1), x.imag.reshape(-1))
         elif self.in_side in ("complex", "halfcomplex"):
@@ -264,7 +320,7 @@ class Problem(object):
         return self._gather(ins, self.in_elems, self.in_side)
 
     def _gather(self, arrs, e, side):
-        if self.split:
+        if side.startswith("split"):
             return (arrs[0][e.reshape(-1)] + 1j * arrs[1][e.reshape(-1)]).reshape(e.shape)
         if side in ("complex", "halfcomplex"):
             w = word_offsets(e, side)
@@ -283,17 +339,30 @@ class Problem(object):
     # -- the plan
     def plan(self, fa, arrays):
         """arrays: what the arenas' payloads became (numpy arrays or device tensors), in the order of arenas()"""
-        ins = arrays[:2] if self.split else arrays[:1]
-        outs = arrays if self.inplace else (arrays[2:] if self.split else arrays[1:])
-        r, n, li, lo, fl = len(self.shape), list(self.shape), self.lin, self.lout, fa.ESTIMATE | self.flags
+        ins = arrays[:self.nin]
+        outs = arrays if self.inplace else arrays[self.nin:]
+        fl = fa.ESTIMATE | self.flags
+        if self.guru:
+            d, h = self.dims, self.hdims
+            if self.kind == "c2c" and self.split:
+                assert self.sign == -1
+                return fa.plan_guru64_split_dft(d, h, ins[0], ins[1], outs[0], outs[1], fl)
+            if self.kind == "c2c":
+                return fa.plan_guru64_dft(d, h, ins[0], outs[0], self.sign, fl)
+            if self.kind == "r2c" and self.split:
+                return fa.plan_guru64_split_dft_r2c(d, h, ins[0], outs[0], outs[1], fl)
+            if self.kind == "r2c":
+                return fa.plan_guru64_dft_r2c(d, h, ins[0], outs[0], fl)
+            if self.kind == "c2r" and self.split:
+                return fa.plan_guru64_split_dft_c2r(d, h, ins[0], ins[1], outs[0], fl)
+            if self.kind == "c2r":
+                return fa.plan_guru64_dft_c2r(d, h, ins[0], outs[0], fl)
+            return fa.plan_guru64_r2r(d, h, ins[0], outs[0], self.r2r, fl)
+        r, n, li, lo = len(self.shape), list(self.shape), self.lin, self.lout
         # NULL where the array is the logical shape itself (in place r2c / c2r NULL would mean the padded layout)
         real_inplace = self.inplace and self.kind in ("r2c", "c2r")
         ie = None if li.embed == logical_shape(n, self.in_side) and not real_inplace else list(li.embed)
         oe = None if lo.embed == logical_shape(n, self.out_side) and not real_inplace else list(lo.embed)
-        if self.split:
-            assert self.sign == -1
-            return fa.plan_guru64_split_dft([(n[0], li.stride, lo.stride)], [(self.hm, li.dist, lo.dist)],
-                                            ins[0], ins[1], outs[0], outs[1], fl)
         if self.kind == "c2c":
             return fa.plan_many_dft(r, n, self.hm, ins[0], ie, li.stride, li.dist, outs[0], oe, lo.stride, lo.dist,
                                     self.sign, fl)
@@ -309,7 +378,7 @@ class Problem(object):
     def oracle(self, A):
         """run the oracle on the (numpy) arenas, from and into the payloads"""
         import util
-        assert not self.split
+        assert not self.guru
         li, lo = self.lin, self.lout
         src = A[0].user()                   # contiguous: util.oracle_* pass its memory on as it is
         dst = src if self.inplace else A[1].user()

@@ -7,7 +7,13 @@ executes its plan twice on arenas whose every non-input word is a distinct quiet
   3. a second execute() of the same plan, the arenas re-initialised, leaves bit-identical output arenas,
   4. the input arenas of an out-of-place plan are bit-identical after both, for every kind and whatever the flags.
 
-Every case prints the kernels its plan's sprint() shows; dense cases assert the labels the accuracy matrix pins."""
+Every case prints the kernels its plan's sprint() shows; dense cases assert the labels the accuracy matrix pins.
+Plans of rank 2 and more run in the layouts of footprint_cases.ND_LAYOUTS; the one-trip image and volume steps run in
+their exact layouts, and every other layout must show the step gone (the fallback paths)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -77,3 +83,36 @@ def test_every_r2r_rows_step_is_reached_by_a_non_dense_case_that_passed():
     for lab, cid in sorted(reached.items()):
         print("%-32s %s" % (lab, cid))
     assert sorted(reached) == sorted(FC.R2R_ROWS_STEPS), sorted(set(FC.R2R_ROWS_STEPS) - set(reached))
+
+
+def test_every_nd_family_is_reached_by_a_non_dense_case_that_passed():
+    """every kernel family of the nd table shows in the sprint() of a case of rank >= 2 in a layout whose strides
+    differ from dense (the in-place twin for the steps that exist on dense arrays only: footprint_cases.ND_DENSE_ONLY),
+    that executed and that met the whole pass condition (a lookup after the parametrised test; selected on its own,
+    this test runs the embedded and in-place cases of the nd table itself)"""
+    def sprint_of(c):
+        if c.id not in PASSED and not PASSED_ANY[0] and c.sign < 0 and c.hm <= 3 and not c.host and \
+                (c.layout == "embedded" or c.layout.endswith("-inplace")):
+            _run_and_check(c)
+        return PASSED.get(c.id)
+
+    PASSED_ANY = [bool(PASSED)]
+    reached = FC.nd_family_labels(sprint_of)
+    for f, cid in sorted(reached.items()):
+        print("%-24s %s" % (f, cid))
+    assert sorted(reached) == sorted(FC.ND_FAMILIES), sorted(set(FC.ND_FAMILIES) - set(reached))
+
+
+def test_exchanged_strides_in_place_without_transposition_steps():
+    """FFTW_AMD_NO_TRANSPOSE=1 is read once per process, so its cases run in a child: the in-place plans whose output
+    strides are the input's exchanged, on the element-wise copies, under the same four-part pass condition"""
+    code = ("import sys; sys.path[:0] = %r\n"
+            "import footprint_cases as FC, test_gpu_footprint as T\n"
+            "for c in FC.no_transpose_cases():\n"
+            "    T._run_and_check(c)\n"
+            "    assert 'transpose' not in T.PASSED[c.id], T.PASSED[c.id]\n"
+            "print('checked', len(T.PASSED))\n") % ([FC.AC.ROOT, os.path.join(FC.AC.ROOT, "tests")],)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, FFTW_AMD_NO_TRANSPOSE="1"),
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0 and "checked %d" % len(FC.no_transpose_cases()) in r.stdout, r.stdout
