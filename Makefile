@@ -9,12 +9,14 @@ LIBDIR := fftw3_amd/lib
 CFLAGS := -O2 -fPIC -std=gnu99 -Wall -Wextra -Iinclude -I$(CSRC)
 HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -std=c++17 -Wall
 
-OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/exec.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgr.o $(CSRC)/kernels_vol.o $(CSRC)/kernels_volr.o
+OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/split.o $(CSRC)/exec.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgr.o $(CSRC)/kernels_vol.o $(CSRC)/kernels_volr.o
 
 all: $(LIBDIR)/libfftw3_amd.so
 
-$(CSRC)/%.o: $(CSRC)/%.c $(CSRC)/fa_plan.h $(CSRC)/fa_hip.h $(CSRC)/split_costs.inc $(CSRC)/split_align.inc $(CSRC)/split2_costs.inc $(CSRC)/split2_align.inc include/fftw3.h include/fftw3_amd.h
+$(CSRC)/%.o: $(CSRC)/%.c $(CSRC)/fa_plan.h $(CSRC)/fa_hip.h include/fftw3.h include/fftw3_amd.h
 	$(CC) $(CFLAGS) -c $< -o $@
+# the measured cost tables (tools/perf/fit_split_costs.py writes them) are included by split.c alone
+$(CSRC)/split.o: $(CSRC)/split_costs.inc $(CSRC)/split_align.inc $(CSRC)/split2_costs.inc $(CSRC)/split2_align.inc
 
 # every HIP unit depends on exactly the headers it includes (a full rebuild of the two menu units takes minutes)
 HIPCOMMON := $(CSRC)/common.hpp $(CSRC)/launch.hpp $(CSRC)/butterflies.h $(CSRC)/fa_hip.h include/fftw3_amd.h $(CSRC)/pass1024.hpp
@@ -86,7 +88,7 @@ oracle:
 
 # host-only sanitizer check of the two-trip c2r planner path: the C sources under ASan + UBSan, the HIP units (host-side
 # tables only) from the ordinary library.  Planning needs no device.
-SANSRC := $(CSRC)/api.c $(CSRC)/planner.c $(CSRC)/exec.c $(CSRC)/sharded.c $(CSRC)/slab.c $(CSRC)/slab1d.c $(CSRC)/hostmath.c
+SANSRC := $(CSRC)/api.c $(CSRC)/planner.c $(CSRC)/split.c $(CSRC)/exec.c $(CSRC)/sharded.c $(CSRC)/slab.c $(CSRC)/slab1d.c $(CSRC)/hostmath.c
 san-c2r: $(LIBDIR)/libfftw3_amd.so
 	mkdir -p build
 	$(CC) -O1 -g -std=gnu99 -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -I$(CSRC) tools/san/plan_c2r_decimated.c $(SANSRC) -o build/plan_c2r_decimated_san -L$(LIBDIR) -lfftw3_amd -Wl,-rpath,$(abspath $(LIBDIR)) -lm -lpthread -ldl

@@ -78,6 +78,21 @@ typedef struct {
                              candidate; a knob of its own, not implied by real_img */
 } fa_cfg;
 
+/* The planner's test switches, read from the environment by fa_read_knobs at the top of every fa_build (planner.c)
+   and from nowhere else: one build -- its dry run and its sized runs -- sees one snapshot.  Not part of fa_cfg:
+   wisdom does not store them and a MEASURE candidate, a clone or an FFTW_UNALIGNED twin reads its own when it is
+   built.  Every int is 1 when the variable is PRESENT, whatever its value (FFTW_AMD_NO_TUNED=0 switches the tuned
+   kernels off). */
+typedef struct {
+    int no_tuned, no_3s, no_r1, no_blue_rows, no_narrow, no_split_costs, no_lo_dft, no_img2d, no_r2crows;
+    int r2r_unfused, no_radix4, force_radix4;
+    /* FFTW_AMD_FORCE_LENS="L1,L2,...": n_force_lens >= 2 entries, all >= 1, and their product; 0 entries when the
+       variable is absent, has fewer than two entries or anything but numbers and commas in it.  Entries past
+       FA_MAXPASS are not read. */
+    i64 force_lens[FA_MAXPASS], force_prod;
+    int n_force_lens;
+} fa_knobs;
+
 typedef struct {
     int buf;
     i64 base;
@@ -129,6 +144,7 @@ struct fftw_plan_s {
     int type;                   /* FA_C2C / FA_R2C / FA_C2R / FA_R2R */
     int kinds[FA_MAXRANK];      /* FA_R2R: fftw_r2r_kind of every dim */
     fa_cfg cfg;
+    fa_knobs knobs;             /* snapshot of the test switches this plan's steps were built under */
     int sign;
     unsigned flags;
     int rank;
@@ -213,6 +229,14 @@ int fa_match_transpose(const fa_dim *l, int nl, i64 unit, fa_transp *t);
 /* 1 when *t is square with equal leading dimensions, every batch loop has the same stride on both sides and the
    matrices of the batch do not overlap: the in-place step applies */
 int fa_transp_inplace_ok(const fa_transp *t);
+
+/* split.c: cost models of the multi-pass splits, pure functions of the length */
+int    fa_has_register_kernel(i64 L);
+void   fa_pow2_three_pass_split(i64 n, i64 *lens);
+double fa_mixed_three_pass_split(i64 n, i64 *lens);     /* modelled cost of the split, -1: none */
+void   fa_mixed_two_pass_split(i64 n, i64 *lens);
+double fa_split_cost_measured(i64 L, int pos);          /* 0: no sample */
+double fa_wide_pass_cost(i64 L, int last);              /* 0: no such kernel */
 
 /* exec.c */
 int  fa_device_init(struct fftw_plan_s *p);      /* tables, schedule, scratch; 0 on success */

@@ -34,10 +34,14 @@ typedef struct fftw_plan_s plan;
    256 MiB of scratch in flight): the tail of one lane's launch is filled by the other lane's, and the
    reuse distance of a scratch line is a few transforms instead of a whole 1 GiB launch pair. */
 #define FA_DEFAULT_CHUNK_BYTES ((size_t)128 << 20)
-/* The only process-wide planner setting: the documented setter below (read and written atomically).
-   Everything else a plan is built from lives in the plan's own fa_cfg; the FFTW_AMD_* environment
-   overrides are read into that copy at plan creation, never into shared state, so threads that plan
-   with different settings do not see each other's. */
+/* Where the planner reads the environment -- the block that ends with nt_policy() below, and nowhere else:
+     fa_default_cfg    the tunables of fa_cfg, into the plan's own copy when the plan is created (fa_plan_new);
+     fa_read_knobs     the test switches of fa_knobs, into the plan's own copy at the top of every fa_build;
+     transposes_enabled, nt_policy
+                       FFTW_AMD_NO_TRANSPOSE and FFTW_AMD_NT, once per process, at their first use.
+   Process-wide planner state is therefore those two settings and the documented setter below (read and written
+   atomically); everything else a plan is built from lives in the plan, so threads that plan with different settings
+   do not see each other's, and the builds of one fa_build (a dry run, up to two sized runs) see one environment. */
 static size_t g_chunk_bytes = FA_DEFAULT_CHUNK_BYTES;
 
 void fftw_amd_set_chunk_bytes(size_t nbytes) {
@@ -45,6 +49,7 @@ void fftw_amd_set_chunk_bytes(size_t nbytes) {
 }
 
 static i64 iabs(i64 v) { return v < 0 ? -v : v; }
+static int is_pow2(i64 n) { return (n & (n - 1)) == 0; }
 
 fa_cfg fa_default_cfg(void) {
     fa_cfg c;
@@ -84,6 +89,67 @@ fa_cfg fa_default_cfg(void) {
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
+}
+
+/* The test switches (fa_knobs).  PRESENT: the int at `off` is 1 when the variable exists, whatever it holds -- the
+   rule these hooks have always had.  LENS: the split that FFTW_AMD_FORCE_LENS="L1,L2,..." fixes for the axis whose
+   length is the product (tests/test_gpu_menu.py reaches every kernel variant with it). */
+enum { KNOB_PRESENT, KNOB_LENS };
+static const struct { const char *name; size_t off; int rule; } g_knob_table[] = {
+    { "FFTW_AMD_NO_TUNED",       offsetof(fa_knobs, no_tuned),       KNOB_PRESENT },
+    { "FFTW_AMD_NO_3S",          offsetof(fa_knobs, no_3s),          KNOB_PRESENT },
+    { "FFTW_AMD_NO_R1",          offsetof(fa_knobs, no_r1),          KNOB_PRESENT },
+    { "FFTW_AMD_NO_BLUE_ROWS",   offsetof(fa_knobs, no_blue_rows),   KNOB_PRESENT },
+    { "FFTW_AMD_NO_NARROW",      offsetof(fa_knobs, no_narrow),      KNOB_PRESENT },
+    { "FFTW_AMD_NO_SPLIT_COSTS", offsetof(fa_knobs, no_split_costs), KNOB_PRESENT },
+    { "FFTW_AMD_NO_LO_DFT",      offsetof(fa_knobs, no_lo_dft),      KNOB_PRESENT },
+    { "FFTW_AMD_NO_IMG2D",       offsetof(fa_knobs, no_img2d),       KNOB_PRESENT },
+    { "FFTW_AMD_NO_R2CROWS",     offsetof(fa_knobs, no_r2crows),     KNOB_PRESENT },
+    { "FFTW_AMD_R2R_UNFUSED",    offsetof(fa_knobs, r2r_unfused),    KNOB_PRESENT },
+    { "FFTW_AMD_NO_RADIX4",      offsetof(fa_knobs, no_radix4),      KNOB_PRESENT },
+    { "FFTW_AMD_FORCE_RADIX4",   offsetof(fa_knobs, force_radix4),   KNOB_PRESENT },
+    { "FFTW_AMD_FORCE_LENS",     offsetof(fa_knobs, force_lens),     KNOB_LENS },
+};
+
+static void fa_read_knobs(fa_knobs *k) {
+    size_t i;
+    memset(k, 0, sizeof(*k));
+    for (i = 0; i < sizeof(g_knob_table) / sizeof(g_knob_table[0]); ++i) {
+        const char *c = getenv(g_knob_table[i].name);
+        if (g_knob_table[i].rule == KNOB_PRESENT) {
+            *(int *)((char *)k + g_knob_table[i].off) = c != NULL;
+            continue;
+        }
+        /* at most FA_MAXPASS entries are read (what follows them is not looked at); an entry below 1 or anything
+           but a comma between two entries voids the list, and so does a single entry */
+        k->force_prod = 1;
+        while (c && *c && k->n_force_lens < FA_MAXPASS) {
+            char *end;
+            long long v = strtoll(c, &end, 10);
+            if (end == c || v < 1 || (*end && *end != ',')) { k->n_force_lens = 0; break; }
+            k->force_lens[k->n_force_lens++] = v;
+            k->force_prod *= v;
+            c = (*end == ',') ? end + 1 : end;
+        }
+        if (k->n_force_lens < 2) k->n_force_lens = 0;
+    }
+}
+
+/* FFTW_AMD_NO_TRANSPOSE=1 keeps every copy on the element-wise kernels (measurements: tools/perf/perf_transpose.py).
+   Read once per process, as documented and tested (tests/test_gpu_footprint.py runs it in a child for that reason):
+   fa_match_transpose takes no plan, and api.c calls it outside fa_build too */
+static int transposes_enabled(void) {
+    static int on = -1;
+    if (on < 0) { const char *e = getenv("FFTW_AMD_NO_TRANSPOSE"); on = !(e && atoi(e)); }
+    return on;
+}
+
+/* FFTW_AMD_NT, the cache policy of mark_streaming_accesses: 0 never, 1 by size (default), 2 always.  Read once per
+   process */
+static int nt_policy(void) {
+    static int policy = -1;
+    if (policy < 0) { const char *e = getenv("FFTW_AMD_NT"); policy = e ? atoi(e) : 1; }
+    return policy;
 }
 
 /* ------------------------------------------------------------------ plan */
@@ -450,12 +516,12 @@ static void emit_pass(plan *p, fa_loc src, fa_loc dst, i64 L, i64 is_l, i64 os_l
     if (T < 1) T = 1;
     s->tile = (int)T;
     if (src.im == 1 && dst.im == 1 && !(flags & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT)) &&
-        !getenv("FFTW_AMD_NO_TUNED")) {
+        !p->knobs.no_tuned) {
         if (L == 1024) {
             s->variant = FFTW_AMD_K_P1024;  /* register-resident radix-32x32, 8 sequences per tile */
             s->tile = 8;
         } else if (L <= 32 && fa_hip_r1_tile((int)L) > 0 && is_l == 2 && os_l == 2 && tw_n == 0 && s->tile_lo_n == 1 &&
-                   s->dim_is[0] == 2 * L && s->dim_os[0] == 2 * L && s->dim_n[0] >= 256 && !getenv("FFTW_AMD_NO_R1")) {
+                   s->dim_is[0] == 2 * L && s->dim_os[0] == 2 * L && s->dim_n[0] >= 256 && !p->knobs.no_r1) {
             s->variant = FFTW_AMD_K_R1;     /* dense rows of a short length: one butterfly per row (pass1r.hpp) */
             s->tile = fa_hip_r1_tile((int)L);
         } else if (fa_hip_r3_tile((int)L) > 0 && is_l == 2 && os_l == 2 && tw_n == 0 && s->tile_lo_n == 1 &&
@@ -463,7 +529,7 @@ static void emit_pass(plan *p, fa_loc src, fa_loc dst, i64 L, i64 is_l, i64 os_l
             s->variant = FFTW_AMD_K_R3;     /* three-stage register kernel, whole contiguous rows */
             s->tile = fa_hip_r3_tile((int)L);
         } else if (fa_hip_rr_tile((int)L) > 0 && s->dim_n[0] * s->tile_lo_n * 4 >= fa_hip_rr_tile((int)L) &&
-                   (s->tile_lo_n == 1 || (L & (L - 1)) == 0)) {
+                   (s->tile_lo_n == 1 || is_pow2(L))) {
             s->variant = FFTW_AMD_K_RR;     /* two-stage register kernel */
             s->tile = fa_hip_rr_tile((int)L);
         } else if (fa_hip_r3t_tile((int)L) > 0 && s->tile_lo_n == 1 && s->dim_n[0] * 4 >= fa_hip_r3t_tile((int)L)) {
@@ -497,13 +563,6 @@ static void emit_copy(plan *p, int kind, fa_loc src, fa_loc dst, i64 K, i64 Kval
 }
 
 /* ------------------------------------------------------- transpositions */
-
-/* FFTW_AMD_NO_TRANSPOSE=1 keeps every copy on the element-wise kernels (measurements: tools/perf/perf_transpose.py) */
-static int transposes_enabled(void) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("FFTW_AMD_NO_TRANSPOSE"); on = !(e && atoi(e)); }
-    return on;
-}
 
 int fa_match_transpose(const fa_dim *l, int nl, i64 unit, fa_transp *t) {
     int ti, i, a, b;
@@ -598,7 +657,6 @@ static int transp_layout_ok(const plan *p, fa_loc src, fa_loc dst) {
 /* ------------------------------------------------------------- one axis */
 
 static void fa_emit_axis(plan *p, const fa_axis *ax);
-static int has_register_kernel(i64 L);
 
 /* the loops of an axis as step dims d[0 ... nloops); lis / los: the loop strides on the two sides when a side is a
    scratch image, NULL = the axis's own .is / .os.  Returns the count, so a caller that put nd dims of its own first
@@ -828,149 +886,6 @@ static void emit_rader(plan *p, const fa_axis *ax) {
     buf_release(p, w.buf);
 }
 
-/* lengths with a register kernel (pass1024 / passrr) */
-static int has_register_kernel(i64 L) {
-    return L == 1024 || (L <= 1024 && (fa_hip_rr_tile((int)L) > 0 || fa_hip_r3t_tile((int)L) > 0));
-}
-
-/* Three-pass split of a contiguous power of two (n >= 2^21).  The balanced split is not the
-   fastest: per-pass times differ by position (first: long input stride; middle: in place at a
-   medium stride; last: contiguous rows in, transposed out) and by tile width -- the 256-point
-   kernel (16-wide tiles) is the slow one in the first two positions, short middle passes with
-   64 ... 256-wide tiles the fast ones.  Costs: ms per 4 GiB moved, measured on MI355X
-   (tests/perf_p512.py); unmeasured positions carry a pessimistic guess. */
-static void pow2_three_pass_split(i64 n, i64 *lens) {
-    /*                              2^4   2^5   2^6   2^7   2^8   2^9   2^10 */
-    static const double c_first[] = { 1.00, 1.00, 0.95, 0.80, 1.02, 0.87, 1.30 };
-    static const double c_mid[]   = { 0.77, 0.78, 0.75, 0.76, 0.99, 0.90, 1.02 };
-    static const double c_last[]  = { 0.95, 0.95, 0.90, 0.80, 0.80, 0.82, 0.84 };
-    int e = 0, a, m, c, ba = 0, bm = 0, bc = 0;
-    double best = 1e30;
-    while (((i64)1 << e) < n) ++e;
-    for (a = 4; a <= 10; ++a)
-        for (m = 4; m <= 10; ++m) {
-            double t;
-            c = e - a - m;
-            if (c < 4 || c > 10) continue;
-            t = c_first[a - 4] + c_mid[m - 4] + c_last[c - 4];
-            {   /* near-ties go to the more balanced split */
-                int hi = a > m ? (a > c ? a : c) : (m > c ? m : c), lo = a < m ? (a < c ? a : c) : (m < c ? m : c);
-                t += 0.01 * (hi - lo);
-            }
-            if (t < best - 1e-9) { best = t; ba = a; bm = m; bc = c; }
-        }
-    if (!ba) return;
-    lens[0] = (i64)1 << ba;
-    lens[1] = (i64)1 << bm;
-    lens[2] = (i64)1 << bc;
-}
-
-/* Three-pass split of a contiguous length that is not a power of two.  The balanced split the
-   factoriser returns is rarely the fastest: the register kernels differ by up to 1.5x from one
-   sub-transform length to the next (tile width, ragged tiles, radix mix) and by position (first:
-   long input stride; middle: in place; last: rows in, transposed out).  Costs are measured
-   medians, ms per GiB of a pass (split_costs.inc); the additive model picks the measured best
-   split for 5 of the 8 lengths it was checked on and is within 1-7 % on the others
-   (tools/perf/fit_split_costs.py).  Reference counterpart: the planner's choice among
-   ct-dit radices by estimated cost (fftw/fftw_api.c:15300-15426). */
-typedef struct { int L; double c[3]; } split_cost;
-static const split_cost g_split_costs[] = {
-#include "split_costs.inc"
-};
-static double split_cost_of(i64 L, int pos) {
-    const int n = (int)(sizeof(g_split_costs) / sizeof(g_split_costs[0]));
-    int i;
-    for (i = 0; i < n - 1; ++i)
-        if (g_split_costs[i].L == L && g_split_costs[i].c[pos] > 0.0) return g_split_costs[i].c[pos];
-    return g_split_costs[n - 1].c[pos];
-}
-/* the measured value only: 0 when the table has no sample for (L, pos) */
-static double split_cost_measured(i64 L, int pos) {
-    const int n = (int)(sizeof(g_split_costs) / sizeof(g_split_costs[0]));
-    int i;
-    for (i = 0; i < n - 1; ++i)
-        if (g_split_costs[i].L == L) return g_split_costs[i].c[pos];
-    return 0.0;
-}
-/* factor on the first (row 0) / last (row 1) pass by min(5, v2(stride)): their strided side moves runs of
-   T x 16 bytes that start at multiples of the stride, and runs that do not start on a 128-byte line cost up
-   to 1.3x (tools/perf/fit_split_costs.py) */
-static const double g_split_align[2][6] = {
-#include "split_align.inc"
-};
-static int v2_capped(i64 x) { int k = 0; while (k < 5 && (x & 1) == 0) { x >>= 1; ++k; } return k; }
-
-/* returns the modelled cost of the split it chose (ms per GiB of a pass, three passes), -1 if none.
-   Candidates whose FIRST length is a multiple of 8 come first: with an odd or barely even first length the
-   two later passes ran up to 1.3x slower than their lengths' medians in the sweeps (their loops over the first
-   pass's output index then start off the 128-byte grid); restricted to L1 % 8 == 0 the model's pick is within
-   4.3 % of the measured best on all ten lengths of the sweep, unrestricted it misses by up to 34 %. */
-static double mixed_three_pass_split(i64 n, i64 *lens) {
-    static const int need[4] = { 8, 4, 2, 1 };
-    int level;
-    for (level = 0; level < 4; ++level) {
-        i64 a, c;
-        double best = -1.0;
-        for (a = 16; a <= 1024; ++a) {
-            if (n % a || a % need[level] || !has_register_kernel(a)) continue;
-            for (c = 16; c <= 1024; ++c) {
-                i64 m, lo, hi;
-                double cost;
-                if ((n / a) % c || !has_register_kernel(c)) continue;
-                m = n / a / c;
-                if (m < 16 || m > 1024 || !has_register_kernel(m)) continue;
-                lo = a < c ? a : c; if (m < lo) lo = m;
-                hi = a > c ? a : c; if (m > hi) hi = m;
-                if (hi > 4 * lo) continue;
-                cost = split_cost_of(a, 0) * g_split_align[0][v2_capped(m * c)] + split_cost_of(m, 1) +
-                       split_cost_of(c, 2) * g_split_align[1][v2_capped(a * m)];
-                if (best < 0.0 || cost < best) { best = cost; lens[0] = a; lens[1] = m; lens[2] = c; }
-            }
-        }
-        if (best >= 0.0) return best;
-    }
-    return -1.0;
-}
-
-/* Two-pass split n = L1 x L2 by the measured model of tools/perf/fit_split_costs.py (split2_costs.inc: median cost of
-   every menu length as first / last pass over 919 timed plans of 78 lengths; split2_align.inc: the price of strided
-   runs that start off the 128-byte grid, which depends on the OTHER length's factors of two and on the tile width T:
-   cost = c * (1 + 8 / T * m[v2(other)])).  Against the measured best split: mean +0.8 %, worst +9.8 %; the balanced
-   split it replaces: mean +9.6 %, worst +43 % (65 536 = 128 x 512 instead of 256 x 256: 2.67 vs 3.07 ms per 4 GiB). */
-static const split_cost g_split2_costs[] = {
-#include "split2_costs.inc"
-};
-static const double g_split2_align[2][6] = {
-#include "split2_align.inc"
-};
-static double split2_cost_of(i64 L, int pos) {
-    const int n = (int)(sizeof(g_split2_costs) / sizeof(g_split2_costs[0]));
-    int i;
-    for (i = 0; i < n - 1; ++i)
-        if (g_split2_costs[i].L == L && g_split2_costs[i].c[pos] > 0.0) return g_split2_costs[i].c[pos];
-    return g_split2_costs[n - 1].c[pos];
-}
-static int split_tile_of(i64 L) {
-    int t = L == 1024 ? 8 : fa_hip_rr_tile((int)L);
-    if (t <= 0) t = fa_hip_r3t_tile((int)L);
-    return t > 0 ? t : 8;
-}
-static void mixed_two_pass_split(i64 n, i64 *lens) {
-    i64 a;
-    double best = -1.0;
-    for (a = 16; a <= 1024; ++a) {
-        i64 b;
-        double cost;
-        if (n % a || !has_register_kernel(a)) continue;
-        b = n / a;
-        if (b < 16 || b > 1024 || !has_register_kernel(b)) continue;
-        if (a > 8 * b || b > 8 * a) continue;
-        cost = split2_cost_of(a, 0) * (1.0 + 8.0 / split_tile_of(a) * g_split2_align[0][v2_capped(b)]) +
-               split2_cost_of(b, 1) * (1.0 + 8.0 / split_tile_of(b) * g_split2_align[1][v2_capped(a)]);
-        if (best < 0.0 || cost < best) { best = cost; lens[0] = a; lens[1] = b; }
-    }
-}
-
 static int rows_alias_ok(const plan *p, const fa_axis *ax, fa_loc a, fa_loc b);
 
 /* May a contiguous axis longer than FA_LMAX_SINGLE run as ONE trip of a register rows kernel?  Such a step has
@@ -1006,7 +921,7 @@ static int emit_bluestein_rows(plan *p, const fa_axis *ax) {
     int nb, j;
     sdim d[FA_MAXLOOPS];
     fftw_amd_step_desc *s;
-    if (getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_3S") || getenv("FFTW_AMD_NO_BLUE_ROWS")) return 0;
+    if (p->knobs.no_tuned || p->knobs.no_3s || p->knobs.no_blue_rows) return 0;
     if (ax->n < 2 || need > 16384 || ax->nloops == 0) return 0;
     nb = fa_hip_blue_nb((int)need);
     if (nb <= 0 || (double)nb > 1.35 * (double)need) return 0;
@@ -1030,182 +945,176 @@ static int emit_bluestein_rows(plan *p, const fa_axis *ax) {
     return 1;
 }
 
-/* cost of a pass of L points on the 512-item strided / transposed three-stage kernels (r3tw_menu.inc), in ms per
-   GiB moved like split_costs.inc: last = 0 first pass (columns), 1 last pass (rows in, transposed store, twiddle on
-   the input).  Measured with tools/perf/perf_pow2_two_trip.py (profiles/r03_two_trip_wide.txt), taking the two
-   2048-point passes as equal; 0: no such kernel */
-static double wide_pass_cost(i64 L, int last) {
-    static const struct { int L; double first, last; } c[] = {
-        { 2048, 0.239, 0.239 }, { 2000, 0.247, 0.247 }, { 1920, 0.185, 0.207 }, { 1600, 0.265, 0.265 },
-        { 1536, 0.274, 0.290 }, { 1440, 0.339, 0.339 }, { 1280, 0.227, 0.198 }, { 1200, 0.300, 0.300 },
-        { 1080, 0.269, 0.298 },
-    };
-    size_t i;
-    if (L <= 1024 || fa_hip_r3t_tile((int)L) < 8) return 0.0;
-    for (i = 0; i < sizeof(c) / sizeof(c[0]); ++i)
-        if (c[i].L == L) return last ? c[i].last : c[i].first;
-    return 0.0;
+/* ---- how an axis is split into passes: axis_split and its three stages.  They decide and emit nothing. */
+
+/* interleaved complex data on both sides of the axis, no real side: what the tuned complex kernels take */
+static int plain_complex_axis(const fa_axis *ax) {
+    return ax->src.im == 1 && ax->dst.im == 1 &&
+           !((ax->flags_in | ax->flags_out) & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT));
 }
 
-static void fa_emit_axis(plan *p, const fa_axis *ax_in) {
-    fa_axis ax = *ax_in;
-    i64 lens[FA_MAXPASS];
-    int k, contiguous;
-    sdim d[FA_MAXLOOPS];
-    i64 lmax1;
+/* unit-stride rows of a length the three-stage rows kernel does in one trip */
+static int rows3_layout_ok(const plan *p, const fa_axis *ax) {
+    return fa_hip_r3_tile((int)ax->n) > 0 && iabs(ax->is) == 2 && iabs(ax->os) == 2 && plain_complex_axis(ax) &&
+           !p->knobs.no_3s;
+}
 
-    if (p->failed) return;
-
-    if (!fa_lds_able(ax.n)) {
-        if (emit_bluestein_rows(p, &ax)) return;
-        if (fa_is_prime(ax.n) && fa_lds_able(ax.n - 1)) emit_rader(p, &ax);
-        else emit_bluestein(p, &ax);
-        return;
-    }
+/* Stage 1: the longest length the axis may run as ONE pass.  The order of the rules is behaviour: later ones
+   overwrite what earlier ones set. */
+static i64 single_pass_cap(const plan *p, const fa_axis *ax, int contiguous) {
+    const i64 n = ax->n;
+    const int tuned = !p->knobs.no_tuned;
     /* A strided axis keeps tiles at least 8 wide so that global access stays
        in 128-byte segments; a contiguous axis may fill the tile by itself. */
-    contiguous = (iabs(ax.is) <= 2 && iabs(ax.os) <= 2) || ax.dense;
-    lmax1 = contiguous ? FA_LMAX_SINGLE : FA_TILE_ELEMS / 8;
+    i64 lmax1 = contiguous ? FA_LMAX_SINGLE : FA_TILE_ELEMS / 8;
     /* a strided axis with a register kernel of its own length needs no split either */
-    if (!contiguous && ax.n <= 1024 && !getenv("FFTW_AMD_NO_TUNED") && has_register_kernel(ax.n)) lmax1 = 1024;
+    if (!contiguous && n <= 1024 && tuned && fa_has_register_kernel(n)) lmax1 = 1024;
     /* ... and neither does a strided axis of 1025 ... 2048 points with a narrow-tile three-stage kernel
        (4 ... 7 sequences per tile, 64 ... 112-byte segments, ~3 TB/s): the 1080 of a 1080 x 1920 image */
-    if (!contiguous && ax.n > 1024 && ax.n <= 2048 && ax.nloops > 0 && !getenv("FFTW_AMD_NO_TUNED") && !getenv("FFTW_AMD_NO_NARROW") &&
-        fa_hip_r3t_tile((int)ax.n) > 0 && ax.src.im == 1 && ax.dst.im == 1 &&
-        !((ax.flags_in | ax.flags_out) & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT)))
+    if (!contiguous && n > 1024 && n <= 2048 && ax->nloops > 0 && tuned && !p->knobs.no_narrow &&
+        fa_hip_r3t_tile((int)n) > 0 && plain_complex_axis(ax))
         lmax1 = 2048;
     /* powers of two above 1024 run faster as two register-kernel passes than
        as one LDS-sized pass (measured: 4096-point rows 0.8 TB/s vs ~5 TB/s per pass) */
-    if (contiguous && ax.n > 1024 && (ax.n & (ax.n - 1)) == 0 && ax.nloops > 0 &&
-        !getenv("FFTW_AMD_NO_TUNED")) {
+    if (contiguous && n > 1024 && is_pow2(n) && ax->nloops > 0 && tuned) {
         /* ... except contiguous rows of 2048 / 4096: the three-stage kernel does them in one */
-        int rows3s = fa_hip_r3_tile((int)ax.n) > 0 && iabs(ax.is) == 2 && iabs(ax.os) == 2 &&
-                     ax.src.im == 1 && ax.dst.im == 1 &&
-                     !((ax.flags_in | ax.flags_out) & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT)) &&
-                     !getenv("FFTW_AMD_NO_3S");
+        int rows3s = rows3_layout_ok(p, ax);
         /* 8192: one row per workgroup (32 x 16 x 16), one trip instead of 128 x 64 in two; 16384: one row per
            512-item workgroup (pass3w.hpp) */
-        if (rows3s && ax.n > FA_LMAX_SINGLE) rows3s = ax.n <= 16384 && long_rows_ok(p, &ax);
+        if (rows3s && n > FA_LMAX_SINGLE) rows3s = n <= 16384 && long_rows_ok(p, ax);
         if (!rows3s) lmax1 = 1024;
-        else if (ax.n > lmax1) lmax1 = ax.n;
+        else if (n > lmax1) lmax1 = n;
     }
-    if (ax.nloops == 0 && !contiguous) lmax1 = FA_LMAX_SINGLE;
-    /* 1024 < n <= 4096 that is not a power of two: two register-kernel passes (each near
-       the copy rate) beat one pass of the LDS kernel (1.3-1.8 TB/s) whenever both halves of
-       a balanced split have a register kernel -- measured n = 3000: 1.27 vs 2.4 TB/s */
+    if (ax->nloops == 0 && !contiguous) lmax1 = FA_LMAX_SINGLE;
     /* 4096 < n < 16384 with a three-stage rows kernel (one row per workgroup; above 8192 the 512-item kernels of
        kernels_r3w.hip): one trip instead of two, under the same plan-time conditions as the 8192-point rows (no
        LDS-kernel fallback at that length) */
-    if (contiguous && ax.n > FA_LMAX_SINGLE && ax.n < 16384 && (ax.n & (ax.n - 1)) != 0 && ax.nloops > 0 &&
-        !getenv("FFTW_AMD_NO_TUNED") && !getenv("FFTW_AMD_NO_3S") && fa_hip_r3_tile((int)ax.n) > 0 &&
-        long_rows_ok(p, &ax))
-        lmax1 = ax.n;
-    if (contiguous && ax.n > 1024 && ax.n <= lmax1 && (ax.n & (ax.n - 1)) != 0 && ax.nloops > 0 &&
-        !getenv("FFTW_AMD_NO_TUNED") &&
-        /* ... unless the three-stage rows kernel does the whole length in one trip */
-        !(fa_hip_r3_tile((int)ax.n) > 0 && iabs(ax.is) == 2 && iabs(ax.os) == 2 && ax.src.im == 1 &&
-          ax.dst.im == 1 && !((ax.flags_in | ax.flags_out) & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT)) &&
-          !getenv("FFTW_AMD_NO_3S"))) {
+    if (contiguous && n > FA_LMAX_SINGLE && n < 16384 && !is_pow2(n) && ax->nloops > 0 && tuned && !p->knobs.no_3s &&
+        fa_hip_r3_tile((int)n) > 0 && long_rows_ok(p, ax))
+        lmax1 = n;
+    /* 1024 < n <= 4096 that is not a power of two: two register-kernel passes (each near
+       the copy rate) beat one pass of the LDS kernel (1.3-1.8 TB/s) whenever both halves of
+       a balanced split have a register kernel -- measured n = 3000: 1.27 vs 2.4 TB/s --
+       unless the three-stage rows kernel does the whole length in one trip */
+    if (contiguous && n > 1024 && n <= lmax1 && !is_pow2(n) && ax->nloops > 0 && tuned && !rows3_layout_ok(p, ax)) {
         i64 l2[FA_MAXPASS];
-        if (fa_factor_passes_pref(ax.n, 2, 1, 1024, l2, has_register_kernel) == 2 &&
-            has_register_kernel(l2[0]) && has_register_kernel(l2[1]))
+        if (fa_factor_passes_pref(n, 2, 1, 1024, l2, fa_has_register_kernel) == 2 &&
+            fa_has_register_kernel(l2[0]) && fa_has_register_kernel(l2[1]))
             lmax1 = 1024;
     }
-    k = fa_factor_passes_pref(ax.n, FA_MAXPASS, lmax1, contiguous ? p->cfg.lmax_multi : FA_TILE_ELEMS / 8, lens,
-                              getenv("FFTW_AMD_NO_TUNED") ? NULL : has_register_kernel);
-    /* n = L1 x L2 with 1024 < L1 <= 2048 in TWO trips instead of three: the strided three-stage kernel of
-       such a length works on tiles of 4 ... 7 columns (64 ... 112-byte segments, ~3.2 TB/s) -- slower per trip
-       than the 128-byte kernels, but two trips beat three (2^21 = 2048 x 1024: 7.9 vs 11.2 ms per 8 GiB; with
-       BOTH lengths above 1024 the two slow trips only tie with three fast ones, so that is not done) */
-    /* (the narrow-tile kernel takes interleaved complex data on 16-byte aligned arrays only -- the same
-       conditions as for a strided axis above; with split or unaligned arrays its pass would fall to the
-       runtime-radix LDS kernel with a 1 ... 2 column tile, far slower than the three-pass plan) */
-    if (k == 3 && contiguous && ax.nloops > 0 && !getenv("FFTW_AMD_NO_TUNED") && !getenv("FFTW_AMD_NO_NARROW") &&
-        ax.src.im == 1 && ax.dst.im == 1 && !(p->flags & FFTW_UNALIGNED) && p->cfg.lmax_multi >= 1024 &&
-        !((ax.flags_in | ax.flags_out) & (FFTW_AMD_F_REAL_IN | FFTW_AMD_F_REAL_OUT))) {
-        /* cost per GiB of a pass (the units of split_costs.inc): narrow-tile first pass 0.34 (2048-point: 5.33 ms
-           per 16 GiB), the partner as LAST pass from the table (1024: 0.18, the cfg2 pass; 1000: 0.20); the
-           three-pass alternative from the same table (powers of two: 0.68, measured 2^21 ... 2^24) */
-        i64 L1, bestL1 = 0, l3[FA_MAXPASS];
-        double best2 = 1e30, est3 = 0.68;
-        if ((ax.n & (ax.n - 1)) != 0) {
-            double c3 = mixed_three_pass_split(ax.n, l3);
-            if (c3 > 0.0) est3 = c3;
+    return lmax1;
+}
+
+/* Stage 2: n = L1 x L2 with 1024 < L1 <= 2048 in TWO trips instead of the three the factoriser found: the strided
+   three-stage kernel of such a length works on tiles of 4 ... 7 columns (64 ... 112-byte segments, ~3.2 TB/s) --
+   slower per trip than the 128-byte kernels, but two trips beat three (2^21 = 2048 x 1024: 7.9 vs 11.2 ms per 8 GiB;
+   with BOTH lengths above 1024 the two slow trips only tie with three fast ones, so that is not done).
+   (The narrow-tile kernel takes interleaved complex data on 16-byte aligned arrays only -- the same conditions as
+   for a strided axis in single_pass_cap; with split or unaligned arrays its pass would fall to the runtime-radix
+   LDS kernel with a 1 ... 2 column tile, far slower than the three-pass plan.)  1 and lens[0 .. 2) when two trips
+   win. */
+static int two_trip_split(const plan *p, const fa_axis *ax, i64 *lens) {
+    /* cost per GiB of a pass (the units of split_costs.inc): narrow-tile first pass 0.34 (2048-point: 5.33 ms
+       per 16 GiB), the partner as LAST pass from the table (1024: 0.18, the cfg2 pass; 1000: 0.20); the
+       three-pass alternative from the same table (powers of two: 0.68, measured 2^21 ... 2^24) */
+    const i64 n = ax->n;
+    i64 L1, bestL1 = 0, l3[FA_MAXPASS];
+    double best2 = 1e30, est3 = 0.68;
+    if (ax->nloops == 0 || p->knobs.no_tuned || p->knobs.no_narrow || !plain_complex_axis(ax) ||
+        (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
+        return 0;
+    if (!is_pow2(n)) {
+        double c3 = fa_mixed_three_pass_split(n, l3);
+        if (c3 > 0.0) est3 = c3;
+    }
+    for (L1 = 2048; L1 > 1024; --L1) {
+        i64 L2 = n / L1;
+        double c1, c2;
+        if (n % L1 || fa_hip_r3t_tile((int)L1) <= 0 || L2 < 96) continue;
+        /* round 3: the 512-item kernels of r3tw_menu.inc (8 ... 15 sequences per tile) are cheaper first passes
+           than the narrow tiles, and serve as LAST pass too (rows in, transposed store, twiddle on the input):
+           both lengths above 1024, e.g. 2^22 = 2048 x 2048 in 3.8 instead of 5.4 ms per 4 GiB */
+        c1 = fa_wide_pass_cost(L1, 0);
+        if (c1 <= 0.0) c1 = 0.34;
+        if (L2 > 1024) {
+            c2 = L2 <= 2048 ? fa_wide_pass_cost(L2, 1) : 0.0;
+            if (c2 <= 0.0 || fa_wide_pass_cost(L1, 0) <= 0.0) continue;
+        } else {
+            if (!fa_has_register_kernel(L2)) continue;
+            c2 = L2 == 1024 ? 0.18 : (L2 == 1000 ? 0.20 : fa_split_cost_measured(L2, 2));
         }
-        for (L1 = 2048; L1 > 1024; --L1) {
-            i64 L2 = ax.n / L1;
-            double c1, c2;
-            if (ax.n % L1 || fa_hip_r3t_tile((int)L1) <= 0 || L2 < 96) continue;
-            /* round 3: the 512-item kernels of r3tw_menu.inc (8 ... 15 sequences per tile) are cheaper first passes
-               than the narrow tiles, and serve as LAST pass too (rows in, transposed store, twiddle on the input):
-               both lengths above 1024, e.g. 2^22 = 2048 x 2048 in 3.8 instead of 5.4 ms per 4 GiB */
-            c1 = wide_pass_cost(L1, 0);
-            if (c1 <= 0.0) c1 = 0.34;
-            if (L2 > 1024) {
-                c2 = L2 <= 2048 ? wide_pass_cost(L2, 1) : 0.0;
-                if (c2 <= 0.0 || wide_pass_cost(L1, 0) <= 0.0) continue;
-            } else {
-                if (!has_register_kernel(L2)) continue;
-                c2 = L2 == 1024 ? 0.18 : (L2 == 1000 ? 0.20 : split_cost_measured(L2, 2));
-            }
-            if (c2 <= 0.0) continue;                  /* no measurement for that partner: do not guess */
-            if (c1 + c2 < best2) { best2 = c1 + c2; bestL1 = L1; }
-        }
-        if (bestL1 && best2 < 0.95 * est3) { k = 2; lens[0] = bestL1; lens[1] = ax.n / bestL1; }
+        if (c2 <= 0.0) continue;                  /* no measurement for that partner: do not guess */
+        if (c1 + c2 < best2) { best2 = c1 + c2; bestL1 = L1; }
     }
-    /* the measured split models know lengths up to 1024: with a smaller cap (the FFTW_MEASURE candidate
-       lmax_multi = 512, FFTW_AMD_LMAX_MULTI) the balanced split of fa_factor_passes_pref, which honours it, stays */
-    if (p->cfg.lmax_multi < 1024) { /* keep lens */ }
-    else if (k == 3 && contiguous && (ax.n & (ax.n - 1)) == 0 && !getenv("FFTW_AMD_NO_TUNED")) pow2_three_pass_split(ax.n, lens);
-    else if (k == 3 && contiguous && !getenv("FFTW_AMD_NO_TUNED") && !getenv("FFTW_AMD_NO_SPLIT_COSTS")) mixed_three_pass_split(ax.n, lens);
-    else if (k == 2 && contiguous && ax.nloops > 0 && lens[0] <= 1024 && lens[1] <= 1024 && !getenv("FFTW_AMD_NO_TUNED") &&
-             !getenv("FFTW_AMD_NO_SPLIT_COSTS")) mixed_two_pass_split(ax.n, lens);
-    {
-        /* test hook: FFTW_AMD_FORCE_LENS="L1,L2,..." fixes the split of the axis whose length
-           is the product (tests/test_gpu_menu.py reaches every kernel variant with it) */
-        const char *e = getenv("FFTW_AMD_FORCE_LENS");
-        if (e && *e) {
-            i64 fl[FA_MAXPASS], prod = 1;
-            int fk = 0;
-            const char *c = e;
-            while (*c && fk < FA_MAXPASS) {
-                char *end;
-                long long v = strtoll(c, &end, 10);
-                if (end == c || v < 1) { fk = 0; break; }
-                fl[fk++] = v;
-                prod *= v;
-                c = (*end == ',') ? end + 1 : end;
-                if (*end && *end != ',') { fk = 0; break; }
-            }
-            if (fk >= 2 && prod == ax.n) {
-                int a;
-                k = fk;
-                for (a = 0; a < fk; ++a) lens[a] = fl[a];
-            }
-        }
+    if (!bestL1 || !(best2 < 0.95 * est3)) return 0;
+    lens[0] = bestL1;
+    lens[1] = n / bestL1;
+    return 1;
+}
+
+/* Stage 3: the k lengths of a contiguous axis by the measured split model for that k, where there is one (split.c).
+   The models know lengths up to 1024: with a smaller cap (the FFTW_MEASURE candidate lmax_multi = 512,
+   FFTW_AMD_LMAX_MULTI) the balanced split of fa_factor_passes_pref, which honours it, stays. */
+static void measured_split(const plan *p, const fa_axis *ax, int k, i64 *lens) {
+    if (p->cfg.lmax_multi < 1024 || p->knobs.no_tuned) return;
+    if (k == 3 && is_pow2(ax->n)) fa_pow2_three_pass_split(ax->n, lens);
+    else if (k == 3 && !p->knobs.no_split_costs) fa_mixed_three_pass_split(ax->n, lens);
+    else if (k == 2 && ax->nloops > 0 && lens[0] <= 1024 && lens[1] <= 1024 && !p->knobs.no_split_costs)
+        fa_mixed_two_pass_split(ax->n, lens);
+}
+
+/* The split of an LDS-able axis into passes: returns k and lens[0 .. k); 1 = one pass, 0 = no split (Bluestein).
+   contiguous: the axis may fill a tile by itself. */
+static int axis_split(const plan *p, const fa_axis *ax, int contiguous, i64 *lens) {
+    int k = fa_factor_passes_pref(ax->n, FA_MAXPASS, single_pass_cap(p, ax, contiguous),
+                                  contiguous ? p->cfg.lmax_multi : FA_TILE_ELEMS / 8, lens,
+                                  p->knobs.no_tuned ? NULL : fa_has_register_kernel);
+    int a, b;
+    if (contiguous) {
+        if (k == 3 && two_trip_split(p, ax, lens)) k = 2;
+        measured_split(p, ax, k, lens);
     }
-    if (k == 0) {
-        /* e.g. a prime factor between lmax and FA_PRIME_LDS_MAX cannot happen;
-           sizes that do not split fall back to Bluestein */
-        emit_bluestein(p, &ax);
-        return;
+    /* test hook FFTW_AMD_FORCE_LENS (fa_read_knobs): the axis whose length is the product takes that split */
+    if (p->knobs.n_force_lens && p->knobs.force_prod == ax->n) {
+        k = p->knobs.n_force_lens;
+        for (a = 0; a < k; ++a) lens[a] = p->knobs.force_lens[a];
     }
-    if (k == 1) {
-        int nd = loop_sdims(&ax, NULL, NULL, d);
-        emit_pass(p, ax.src, ax.dst, ax.n, ax.is, ax.os, d, nd, 0,
-                  (ax.flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN)) |
-                  (ax.flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT)));
-        return;
-    }
-    if (ax.nloops + k > FFTW_AMD_MAX_DIMS) { p->failed = 1; return; }
-    if (p->cfg.long_first) {
-        /* longest sub-transform first (FFTW_MEASURE candidate) */
-        int a, b;
+    /* longest sub-transform first (FFTW_MEASURE candidate) */
+    if (p->cfg.long_first)
         for (a = 0; a < k; ++a)
             for (b = a + 1; b < k; ++b)
                 if (lens[b] > lens[a]) { i64 t = lens[a]; lens[a] = lens[b]; lens[b] = t; }
+    return k;
+}
+
+static void fa_emit_axis(plan *p, const fa_axis *ax) {
+    i64 lens[FA_MAXPASS];
+    sdim d[FA_MAXLOOPS];
+    int k;
+
+    if (p->failed) return;
+
+    if (!fa_lds_able(ax->n)) {
+        if (emit_bluestein_rows(p, ax)) return;
+        if (fa_is_prime(ax->n) && fa_lds_able(ax->n - 1)) emit_rader(p, ax);
+        else emit_bluestein(p, ax);
+        return;
     }
-    emit_ct(p, &ax, lens, k);
+    k = axis_split(p, ax, (iabs(ax->is) <= 2 && iabs(ax->os) <= 2) || ax->dense, lens);
+    if (k == 0) {
+        /* e.g. a prime factor between lmax and FA_PRIME_LDS_MAX cannot happen;
+           sizes that do not split fall back to Bluestein */
+        emit_bluestein(p, ax);
+        return;
+    }
+    if (k == 1) {
+        emit_pass(p, ax->src, ax->dst, ax->n, ax->is, ax->os, d, loop_sdims(ax, NULL, NULL, d), 0,
+                  (ax->flags_in & (FFTW_AMD_F_SWAP_IN | FFTW_AMD_F_REAL_IN)) |
+                  (ax->flags_out & (FFTW_AMD_F_SWAP_OUT | FFTW_AMD_F_REAL_OUT)));
+        return;
+    }
+    if (ax->nloops + k > FFTW_AMD_MAX_DIMS) { p->failed = 1; return; }
+    emit_ct(p, ax, lens, k);
 }
 
 /* ------------------------------------------------------- whole problems */
@@ -1272,18 +1181,17 @@ static int collect_loops(const plan *p, const fa_dim *dims, int rank, int axis,
    the narrow-tile kernel (64-byte segments, 3.2 TB/s).  The last step has no other executor, so everything it
    needs is settled here: interleaved unit-stride rows, 16-byte aligned arrays, even strides, at most one batch
    loop, no FFTW_UNALIGNED.  1 = emitted. */
-static int has_register_kernel(i64 L);
 static int emit_rows_lo_dft(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     const fa_dim *col = &p->dims[0], *row = &p->dims[1];
     sdim d[3];
     int nd, sbuf;
     i64 N1, N0, T = 0, L0, img, chunk = p->hrank ? p->chunk : 1;
     fftw_amd_step_desc *st;
-    if (p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_LO_DFT") || getenv("FFTW_AMD_NO_3S")) return 0;
+    if (p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_lo_dft || p->knobs.no_3s) return 0;
     N1 = row->n; N0 = col->n;
     if ((N1 != 2048 && N1 != 4096) || N0 <= 1024 || N0 > 4096) return 0;
-    if (N1 == 4096 && N0 <= 2048 && N0 % 2 == 0 && has_register_kernel(N0 / 2)) T = 2;      /* pass3s<16>, XROW */
-    else if (N0 % 4 == 0 && has_register_kernel(N0 / 4)) T = 4;                             /* pass3q / pass3s<8>, XROW */
+    if (N1 == 4096 && N0 <= 2048 && N0 % 2 == 0 && fa_has_register_kernel(N0 / 2)) T = 2;      /* pass3s<16>, XROW */
+    else if (N0 % 4 == 0 && fa_has_register_kernel(N0 / 4)) T = 4;                             /* pass3q / pass3s<8>, XROW */
     if (!T) return 0;
     L0 = N0 / T;
     if (row->is != 2 || row->os != 2 || in.im != 1 || out.im != 1) return 0;
@@ -1339,7 +1247,7 @@ static int emit_images(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, in
     sdim d;
     i64 n0, n1, img;
     int T;
-    if (p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    if (p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
     n0 = col->n; n1 = row->n;
     if (n0 > 64 || n1 > 64) return 0;
     T = (variant == FFTW_AMD_K_IMG2D) ? fa_hip_img2d_tile((int)n0, (int)n1) : fa_hip_img2dl_tile((int)n0, (int)n1);
@@ -1396,7 +1304,7 @@ static int emit_vol3d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     sdim d;
     i64 n0, n1, n2, vol;
     int T;
-    if (!p->cfg.vol3d || p->rank != 3 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    if (!p->cfg.vol3d || p->rank != 3 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
     n0 = d0->n; n1 = d1->n; n2 = d2->n;
     if (n0 > 32 || n1 > 32 || n2 > 32) return 0;
     T = fa_hip_vol3d_tile((int)n0, (int)n1, (int)n2);
@@ -1555,14 +1463,17 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
     }
 }
 
-/* passes a contiguous axis of length n needs (mirrors fa_emit_axis); 99 for
-   lengths that go through Rader / Bluestein */
+/* An estimate of the passes a contiguous axis of length n needs, for the choice between the real-axis plans
+   (use_radix4_real); 99 for lengths that go through Rader / Bluestein.  It is NOT axis_split: of its rules it knows
+   only the first cap (FA_LMAX_SINGLE, 1024 for a tuned power of two above that) and the plain balanced
+   factorisation -- no rows kernels, no register-kernel preference, no two-trip plans, no FFTW_AMD_FORCE_LENS.  The
+   plans that were measured were chosen by this count, so it stays what it is. */
 static int axis_pass_count(const plan *p, i64 n) {
     i64 lens[FA_MAXPASS], lmax1 = FA_LMAX_SINGLE;
     int k;
     if (!fa_lds_able(n)) return 99;
     /* (the radix-4 real plans feed strided pair data: the 3-stage row kernel does not apply) */
-    if (n > 1024 && (n & (n - 1)) == 0 && !getenv("FFTW_AMD_NO_TUNED")) lmax1 = 1024;
+    if (n > 1024 && is_pow2(n) && !p->knobs.no_tuned) lmax1 = 1024;
     k = fa_factor_passes(n, FA_MAXPASS, lmax1, p->cfg.lmax_multi, lens);
     return k ? k : 99;
 }
@@ -1572,13 +1483,13 @@ static int axis_pass_count(const plan *p, i64 n) {
    would put a pass on the runtime-radix LDS kernel (3 932 160 = 4 x 960 x 1024: 7.9 ms per 4 GiB where the half-length
    plan takes 4.3, profiles/r03_r2c_two_trip.txt).  One-pass lengths keep the old rule. */
 static int radix4_passes_have_kernels(const plan *p, i64 m) {
-    return axis_pass_count(p, m) <= 1 || (m & (m - 1)) == 0;
+    return axis_pass_count(p, m) <= 1 || is_pow2(m);
 }
 
 /* passes of the half-length complex transform of an r2c / c2r axis: its rows are contiguous, so a length with
    a three-stage rows kernel (up to 8192) is one pass */
 static int half_axis_pass_count(const plan *p, i64 n) {
-    if (n <= 16384 && !getenv("FFTW_AMD_NO_TUNED") && !getenv("FFTW_AMD_NO_3S") && fa_hip_r3_tile((int)n) > 0) return 1;
+    if (n <= 16384 && !p->knobs.no_tuned && !p->knobs.no_3s && fa_hip_r3_tile((int)n) > 0) return 1;
     return axis_pass_count(p, n);
 }
 
@@ -1607,7 +1518,7 @@ static int rows_alias_ok(const plan *p, const fa_axis *ax, fa_loc a, fa_loc b) {
    that side is then the user's real array of any stride, which the kernel gathers from / scatters to by element */
 static int real_rows_layout_ok(const plan *p, const fa_axis *ax, fa_loc src, fa_loc dst, int hook_in, int hook_out) {
     int j, rows = 0;
-    if (getenv("FFTW_AMD_NO_R2CROWS")) return 0;
+    if (p->knobs.no_r2crows) return 0;
     if (!rows_alias_ok(p, ax, src, dst)) return 0;
     for (j = 0; j < ax->nloops; ++j) {
         if ((!hook_in && (ax->loops[j].is % 2)) || (!hook_out && (ax->loops[j].os % 2))) return 0;
@@ -1625,7 +1536,7 @@ static int real_rows_layout_ok(const plan *p, const fa_axis *ax, fa_loc src, fa_
 /* rows per tile of the one-trip real-rows kernels for half length `half` (0: none): the power-of-two two-stage
    form carries the r2r hooks; its mixed-radix lengths (r2cr_menu.inc) and the three-stage form (640 ... 8192) only
    the plain r2c / c2r */
-static int real_rows_tile(i64 half, int hooks) {
+static int real_rows_tile(const plan *p, i64 half, int hooks) {
     int t;
     if (half > 16384) return 0;
     t = fa_hip_r2c_rows_tile((int)half);
@@ -1633,15 +1544,15 @@ static int real_rows_tile(i64 half, int hooks) {
     if (hooks) return 0;
     t = fa_hip_r2c_rows2m_tile((int)half);
     if (t > 0) return t;
-    if (getenv("FFTW_AMD_NO_3S")) return 0;
+    if (p->knobs.no_3s) return 0;
     return fa_hip_r2c_rows3_tile((int)half);
 }
 
 /* dense real rows of n = 2 half = 4 ... 64 points with at least one tile of them in a loop whose strides are exactly
    the row lengths (n reals, half + 1 complex numbers): the one-stage real-rows kernel (pass1r.hpp); 0: not this */
-static int short_real_rows_tile(const fa_axis *ax, i64 half, int hooks, int fwd) {
+static int short_real_rows_tile(const plan *p, const fa_axis *ax, i64 half, int hooks, int fwd) {
     int j, t;
-    if (hooks || half < 2 || half > 32 || getenv("FFTW_AMD_NO_R1")) return 0;
+    if (hooks || half < 2 || half > 32 || p->knobs.no_r1) return 0;
     t = fa_hip_r2c_rows1_tile((int)half);
     if (t <= 0) return 0;
     for (j = 0; j < ax->nloops; ++j)
@@ -1654,13 +1565,13 @@ static int short_real_rows_tile(const fa_axis *ax, i64 half, int hooks, int fwd)
 }
 
 /* rows per tile of the one-trip rows step of an r2c (fwd) / c2r axis, 0: no such kernel */
-static int real_rows_tile_for(const fa_axis *ax, i64 half, int hooks, int fwd) {
-    const int t = short_real_rows_tile(ax, half, hooks, fwd);
-    return t > 0 ? t : real_rows_tile(half, hooks);
+static int real_rows_tile_for(const plan *p, const fa_axis *ax, i64 half, int hooks, int fwd) {
+    const int t = short_real_rows_tile(p, ax, half, hooks, fwd);
+    return t > 0 ? t : real_rows_tile(p, half, hooks);
 }
 
 /* can the r2c / c2r axis emitters fuse an r2r epilogue / prologue for this length? */
-static int r2r_can_fuse(i64 nl) { return nl >= 2 && nl % 2 == 0 && !getenv("FFTW_AMD_R2R_UNFUSED"); }
+static int r2r_can_fuse(const plan *p, i64 nl) { return nl >= 2 && nl % 2 == 0 && !p->knobs.r2r_unfused; }
 
 /* Twiddle tables of a step that untangles / tangles a real transform of nl points.  Plain: modulus nl.  With a fused
    REDFT/RODFT 10/01 epilogue or prologue: the modulus-4n table serves both the r2r twiddle w_4n^k and the untangle
@@ -1711,9 +1622,9 @@ static void emit_real_rows_step(plan *p, int fwd, i64 nl, const fa_axis *ax, fa_
 /* the radix-4 plans of a real axis (n = 4m, two complex transforms of m points and a radix-4 untangle / tangle) are
    chosen when m needs fewer passes than n / 2; FFTW_AMD_NO_RADIX4 / FFTW_AMD_FORCE_RADIX4 override */
 static int use_radix4_real(const plan *p, i64 nl, const fa_axis *ax) {
-    return nl % 4 == 0 && nl >= 8 && ax->nloops < FA_MAXLOOPS && !getenv("FFTW_AMD_NO_RADIX4") &&
+    return nl % 4 == 0 && nl >= 8 && ax->nloops < FA_MAXLOOPS && !p->knobs.no_radix4 &&
            ((axis_pass_count(p, nl / 4) < half_axis_pass_count(p, nl / 2) && radix4_passes_have_kernels(p, nl / 4)) ||
-            getenv("FFTW_AMD_FORCE_RADIX4"));
+            p->knobs.force_radix4);
 }
 
 /* ---- what the two decimated plans below (emit_r2c_decimated, emit_c2r_decimated) share */
@@ -1726,13 +1637,13 @@ static int use_radix4_real(const plan *p, i64 nl, const fa_axis *ax) {
 static i64 real_dec_geometry(const plan *p, i64 nl, const fa_axis *ax, fa_loc src, fa_loc dst, int fwd) {
     const i64 L2 = FA_DEC_L2, L1 = nl / L2;
     int j;
-    if (!p->cfg.real_dec || (!fwd && p->type != FA_C2R) || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_NARROW") ||
+    if (!p->cfg.real_dec || (!fwd && p->type != FA_C2R) || p->knobs.no_tuned || p->knobs.no_narrow ||
         (p->flags & FFTW_UNALIGNED) || p->cfg.lmax_multi < 1024)
         return 0;
     if (nl % L2 || !(fwd ? fa_hip_r3tw_rdec((int)L2) : fa_hip_r3tw_cdec((int)L2)) || fa_hip_r3t_tile((int)L2) < 8) return 0;
     if (L1 % 2 || L1 < 256) return 0;
     /* a register kernel of that length with 128-byte segments */
-    if (!((L1 <= 1024 && has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
+    if (!((L1 <= 1024 && fa_has_register_kernel(L1)) || (L1 <= 2048 && fa_hip_r3t_tile((int)L1) >= 8))) return 0;
     if (ax->nloops >= FA_MAXLOOPS || src.im != (fwd ? 0 : 1) || dst.im != (fwd ? 1 : 0)) return 0;
     if ((src.base % 2) || (dst.base % 2) || ((size_t)p->ro % 16)) return 0;
     /* (a c2r source may be the scratch image of the leading dims) */
@@ -1890,7 +1801,7 @@ static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs,
         buf_release(p, z.buf);
     } else if (nl % 2 == 0 && nl >= 2 && (pre != 0 || (ps == 2 && pim == 1)) &&
                (epi != 0 || (cs == 2 && out.im == 1)) &&
-               (rows_tile = real_rows_tile_for(&ax, nl / 2, epi || pre, 1)) > 0 &&
+               (rows_tile = real_rows_tile_for(p, &ax, nl / 2, epi || pre, 1)) > 0 &&
                real_rows_layout_ok(p, &ax, in, out, pre, epi)) {
         emit_real_rows_step(p, 1, nl, &ax, in, rs, out, cs, pre, epi, rows_tile);
     } else if (nl % 2 == 0 && nl >= 2) {
@@ -1955,7 +1866,7 @@ static int emit_real_image(plan *p, int fwd) {
     sdim d;
     i64 n0, n1, cp, rp, r_el, c_el, c_row, r_img, c_img;
     int T;
-    if (!p->cfg.real_img || p->rank != 2 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    if (!p->cfg.real_img || p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
     n0 = col->n; n1 = row->n;
     if (n0 > 32 || n1 > 32) return 0;
     T = fa_hip_img2dr_tile((int)n0, (int)n1, fwd);
@@ -2007,7 +1918,7 @@ static int emit_real_volume(plan *p, int fwd) {
     sdim d;
     i64 n0, n1, n2, cp, rp, r_vol, c_vol;
     int T;
-    if (!p->cfg.real_vol || p->rank != 3 || p->hrank > 1 || getenv("FFTW_AMD_NO_TUNED") || getenv("FFTW_AMD_NO_IMG2D")) return 0;
+    if (!p->cfg.real_vol || p->rank != 3 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
     n0 = d0->n; n1 = d1->n; n2 = d2->n;
     if (n0 > 32 || n1 > 32 || n2 > 32) return 0;
     T = fa_hip_vol3dr_tile((int)n0, (int)n1, (int)n2, fwd);
@@ -2172,7 +2083,7 @@ static void emit_c2r_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc cur, i64 c
         buf_release(p, z.buf);
     } else if (nl % 2 == 0 && nl >= 2 && (post != 0 || (ps == 2 && pim == 1)) &&
                (pro != 0 || (cs == 2 && cur.im == 1)) &&
-               (rows_tile = real_rows_tile_for(&ax, nl / 2, pro || post, 0)) > 0 &&
+               (rows_tile = real_rows_tile_for(p, &ax, nl / 2, pro || post, 0)) > 0 &&
                real_rows_layout_ok(p, &ax, cur, out, pro, post)) {
         emit_real_rows_step(p, 0, nl, &ax, cur, cs, out, rs, pro, post, rows_tile);
     } else if (nl % 2 == 0 && nl >= 2) {
@@ -2394,14 +2305,14 @@ static void emit_r2r_axis(plan *p, int kind, i64 n, const fa_axis *axp, fa_loc i
 
     /* even inner length: the untangle / tangle step of the real transform does the
        r2r post / pre processing itself, one pass over the data less */
-    if (inner == IN_R2C && post && r2r_can_fuse(N)) { fuse_post = 1; cntB = 0; }
+    if (inner == IN_R2C && post && r2r_can_fuse(p, N)) { fuse_post = 1; cntB = 0; }
     /* short rows: the fused real-rows kernel also gathers the pre-processed sequence from the
        user's row itself -- the whole r2r axis is one trip */
     if (fuse_post && pre && pre != FFTW_AMD_R2R_PRE_HC2R && fa_hip_r2c_rows_tile((int)(N / 2)) > 0) {
         fa_axis tax = *axp;
         if (real_rows_layout_ok(p, &tax, in, out, pre, post)) { rows_pre = pre; cntA = 0; }
     }
-    if (inner == IN_C2R && pre && r2r_can_fuse(N)) { fuse_pre = 1; cntA = 0; }
+    if (inner == IN_C2R && pre && r2r_can_fuse(p, N)) { fuse_pre = 1; cntA = 0; }
     /* short rows: the fused c2r rows kernel also does the DCT-III / DST-III output shuffle */
     if (fuse_pre && post && fa_hip_r2c_rows_tile((int)(N / 2)) > 0) {
         fa_axis tax = *axp;
@@ -2560,12 +2471,10 @@ static void build_steps(plan *p) {
    Cache (256 MiB) then keeps the scratch image between two passes of a chunk instead of
    input / output lines nobody asks for again (tests/micro/membw3.hip).  Small problems keep
    plain accesses so that a consumer kernel still finds the output on chip. */
-static int g_nt_policy = -1;      /* FFTW_AMD_NT: 0 never, 1 by size (default), 2 always */
 static void mark_streaming_accesses(plan *p) {
     int i, j;
     double touched = ((double)(p->in_hi - p->in_lo) + (double)(p->out_hi - p->out_lo)) * sizeof(double);
-    if (g_nt_policy < 0) { const char *e = getenv("FFTW_AMD_NT"); g_nt_policy = e ? atoi(e) : 1; }
-    if (g_nt_policy == 0 || (g_nt_policy == 1 && touched < 384.0 * 1048576.0)) return;
+    if (nt_policy() == 0 || (nt_policy() == 1 && touched < 384.0 * 1048576.0)) return;
     for (i = 0; i < p->nsteps; ++i) {
         fftw_amd_step_desc *s = &p->steps[i];
         if (s->src_buf == 0) {
@@ -2585,7 +2494,9 @@ static void mark_streaming_accesses(plan *p) {
 static int fa_build_steps_sized(plan *p);
 
 int fa_build(plan *p) {
-    int r = fa_build_steps_sized(p);
+    int r;
+    fa_read_knobs(&p->knobs);
+    r = fa_build_steps_sized(p);
     if (r == 0 && p->batch > 0) mark_streaming_accesses(p);
     return r;
 }

@@ -26,6 +26,35 @@ def test_pins_file_lists_exactly_the_corpus():
     assert sorted(_pins()) == sorted(ids), "tools/plan_dump.py --write regenerates tests/golden/plan_pins.txt"
 
 
+KNOBS = ["FFTW_AMD_" + k for k in (
+    "NO_TUNED", "NO_3S", "NO_R1", "NO_BLUE_ROWS", "NO_NARROW", "NO_SPLIT_COSTS", "NO_LO_DFT", "NO_IMG2D", "NO_R2CROWS",
+    "R2R_UNFUSED", "NO_RADIX4", "FORCE_RADIX4", "FORCE_LENS")]
+
+
+def _plan_text(cid):
+    """the dump of a pinned case without its two header lines (the id and the environment, which always differ)"""
+    case = [c for c in CASES if c[0] == cid]
+    assert len(case) == 1 and cid in _pins(), "%s is not a pinned case" % cid
+    return plan_dump.dump_case(case[0])[0].split("\n", 2)[2]
+
+
+@pytest.mark.parametrize("knob", KNOBS)
+def test_each_knob_flips_a_pinned_plan(knob):
+    """a condition on the corpus, not on the planner: the pins protect a switch only if some pinned case reaches it.
+    The hash of a dump covers the line that names the environment, so the plans themselves are compared."""
+    env = dict((c[0], c[1]) for c in CASES)
+    with_knob, without = plan_dump.KNOB_TWINS[knob]
+    assert knob in env[with_knob] and dict((k, v) for k, v in env[with_knob].items() if k != knob) == env[without]
+    assert _pins()[with_knob].split()[2] != _pins()[without].split()[2]
+    assert _plan_text(with_knob) != _plan_text(without), "%s changes nothing in the plan of %s" % (knob, without)
+
+
+@pytest.mark.parametrize("cid,same_as", plan_dump.KNOB_SAME, ids=[c[0] for c in plan_dump.KNOB_SAME])
+def test_knob_truth_rules(cid, same_as):
+    """presence-tested hooks (=0 still switches the feature off); a malformed or non-matching FORCE_LENS is void"""
+    assert _plan_text(cid) == _plan_text(same_as)
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_plan_is_the_pinned_one(case):
     want = _pins().get(case[0])

@@ -223,7 +223,50 @@ def corpus():
     add("c2c-bluestein-1031x8-no-rows", {"FFTW_AMD_NO_BLUE_ROWS": "1"}, c2c_many, [1031], 8, fa.BACKWARD)
     add("c2c-64x97", {}, c2c_many, [64, 97])
     add("c2c-8x16x32x2", {}, c2c_many, [8, 16, 32], 2)
+
+    # every test switch the planner reads while it builds the steps flips at least one plan (KNOB_TWINS), and the
+    # traps of their truth rules: the NO_* hooks are presence-tested (=0 still switches the feature off);
+    # FORCE_LENS is void when malformed or when its product is not the length, and is read up to four entries only
+    add("c2c-2^22-no-tuned-0", {"FFTW_AMD_NO_TUNED": "0"}, c2c_many, [1 << 22])
+    add("c2c-bluestein-1031x8-no-blue-rows", {"FFTW_AMD_NO_BLUE_ROWS": "1"}, c2c_many, [1031], 8)
+    add("c2c-2^21x2", {}, c2c_many, [1 << 21], 2)
+    add("c2c-2^21x2-no-narrow", {"FFTW_AMD_NO_NARROW": "1"}, c2c_many, [1 << 21], 2)
+    add("c2c-65536x2-no-split-costs", {"FFTW_AMD_NO_SPLIT_COSTS": "1"}, c2c_many, [65536], 2)
+    add("c2c-4096x8-no-3s", {"FFTW_AMD_NO_3S": "1"}, c2c_many, [4096], 8)
+    add("c2c-2048x2048", {}, c2c_many, [2048, 2048])
+    add("c2c-2048x2048-no-lo-dft", {"FFTW_AMD_NO_LO_DFT": "1"}, c2c_many, [2048, 2048])
+    add("c2c-16x16x64", {}, c2c_many, [16, 16], 64)
+    add("c2c-16x16x64-no-img2d", {"FFTW_AMD_NO_IMG2D": "1"}, c2c_many, [16, 16], 64)
+    add("c2c-4096x8-force-64x64", {"FFTW_AMD_FORCE_LENS": "64,64"}, c2c_many, [4096], 8)
+    add("c2c-4096x8-force-malformed", {"FFTW_AMD_FORCE_LENS": "32,x"}, c2c_many, [4096], 8)
+    add("c2c-4096x8-force-other-product", {"FFTW_AMD_FORCE_LENS": "64,32"}, c2c_many, [4096], 8)
+    add("c2c-4096x8-force-five-entries", {"FFTW_AMD_FORCE_LENS": "8,8,8,8,2"}, c2c_many, [4096], 8)
     return cases
+
+
+# knob -> (a case planned with it, the same problem's case without it): their plans differ (tests/test_plan_pins.py)
+KNOB_TWINS = {
+    "FFTW_AMD_NO_TUNED": ("c2c-2^22-no-tuned", "c2c-2^22"),
+    "FFTW_AMD_NO_3S": ("c2c-4096x8-no-3s", "c2c-4096x8"),
+    "FFTW_AMD_NO_R1": ("r2c-16x256-no-r1", "r2c-16x256"),
+    "FFTW_AMD_NO_BLUE_ROWS": ("c2c-bluestein-1031x8-no-blue-rows", "c2c-bluestein-rows-1031x8"),
+    "FFTW_AMD_NO_NARROW": ("c2c-2^21x2-no-narrow", "c2c-2^21x2"),
+    "FFTW_AMD_NO_SPLIT_COSTS": ("c2c-65536x2-no-split-costs", "c2c-65536x2"),
+    "FFTW_AMD_NO_LO_DFT": ("c2c-2048x2048-no-lo-dft", "c2c-2048x2048"),
+    "FFTW_AMD_NO_IMG2D": ("c2c-16x16x64-no-img2d", "c2c-16x16x64"),
+    "FFTW_AMD_NO_R2CROWS": ("r2c-512x8-norows", "r2c-512x8"),
+    "FFTW_AMD_R2R_UNFUSED": ("r2r-redft10-128x256-unfused", "r2r-redft10-128x256"),
+    "FFTW_AMD_NO_RADIX4": ("r2c-2^22-no-radix4", "r2c-2^22"),
+    "FFTW_AMD_FORCE_RADIX4": ("r2c-4x6x64-force4", "r2c-4x6x64"),
+    "FFTW_AMD_FORCE_LENS": ("c2c-4096x8-force-64x64", "c2c-4096x8"),
+}
+
+# (case, the case whose plan it must equal): what the truth rules make of a switch's value
+KNOB_SAME = [
+    ("c2c-2^22-no-tuned-0", "c2c-2^22-no-tuned"),
+    ("c2c-4096x8-force-malformed", "c2c-4096x8"),
+    ("c2c-4096x8-force-other-product", "c2c-4096x8"),
+]
 
 
 # ---------------------------------------------------------------------- dump
