@@ -64,6 +64,7 @@ F_REAL_IMG = 1 << 18
 F_VOL3D = 1 << 19
 F_REAL_VOL = 1 << 20
 F_PAIR_SWAP = 1 << 16
+F_P1024_EIGHTHS = 1 << 21
 # FFTW_AMD_K_* kernel ids (step.variant of a pass or copy)
 K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL, K_IMG2DR = range(12)
 K_VOL3D = 12
@@ -215,6 +216,7 @@ _sig("fftw_amd_set_chunk_bytes", None, C.c_size_t)
 _sig("fftw_amd_plan_paired", C.c_int, _vp)
 _sig("fftw_amd_plan_lanes", C.c_int, _vp)
 _sig("fftw_amd_p1024_launches", None, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong))
+_sig("fftw_amd_p1024_tile_order", C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong))
 _sig("fftw_amd_set_device", C.c_int, C.c_int)
 _sig("fftw_amd_get_device", C.c_int)
 _sig("fftw_amd_plan_num_steps", C.c_int, _vp)
@@ -247,6 +249,20 @@ def p1024_launches():
     full, general = C.c_longlong(), C.c_longlong()
     lib.fftw_amd_p1024_launches(C.byref(full), C.byref(general))
     return full.value, general.value
+
+
+# tile orders of the 1024-point register pass that the library has (FFTW_AMD_P1024_ORDER = 0 ... orders - 1)
+P1024_ORDERS = lib.fftw_amd_p1024_tile_order(0, 1, None)
+
+
+def p1024_tile_order(order, nblocks):
+    """place[b] in the tile list of workgroup b of a launch of nblocks workgroups under tile order `order`: the
+    kernels' own function, evaluated on the host"""
+    import numpy as np
+    place = np.empty(nblocks, dtype=np.int64)
+    if lib.fftw_amd_p1024_tile_order(order, nblocks, place.ctypes.data_as(C.POINTER(C.c_longlong))) <= 0:
+        raise ValueError("no launch of %d workgroups under tile order %d" % (nblocks, order))
+    return place
 
 
 # enum fa_elem_form (csrc/fa_hip.h), in its order

@@ -83,9 +83,13 @@ typedef struct {
    wisdom does not store them and a MEASURE candidate, a clone or an FFTW_UNALIGNED twin reads its own when it is
    built.  Every int is 1 when the variable is PRESENT, whatever its value (FFTW_AMD_NO_TUNED=0 switches the tuned
    kernels off). */
+#define FA_P1024_ORDER_DEFAULT 1
 typedef struct {
     int no_tuned, no_3s, no_r1, no_blue_rows, no_narrow, no_split_costs, no_lo_dft, no_img2d, no_r2crows;
     int r2r_unfused, no_radix4, force_radix4;
+    int p1024_order;            /* FFTW_AMD_P1024_ORDER: tile order of the 1024-point pass.  The one switch that carries a
+                                   number: FA_P1024_ORDER_DEFAULT when absent or negative, 0 = every XCD walks its eighth of
+                                   the tile list from the start (the steps then carry FFTW_AMD_F_P1024_EIGHTHS) */
     /* FFTW_AMD_FORCE_LENS="L1,L2,...": n_force_lens >= 2 entries, all >= 1, and their product; 0 entries when the
        variable is absent, has fewer than two entries or anything but numbers and commas in it.  Entries past
        FA_MAXPASS are not read. */

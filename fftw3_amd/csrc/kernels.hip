@@ -319,6 +319,7 @@ static int fill_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *co
     pa.flags = d->flags;
     pa.lo_sh = 0; pa.lo_is = d->tile_lo_is; pa.lo_os = d->tile_lo_os;
     pa.dbg = NULL;
+    pa.order = FA_P1024_ORD_EIGHTH;
     if (d->tile_lo_n > 1) {
         if (d->tile_lo_n != 2 && d->tile_lo_n != 4) return 1;
         pa.lo_sh = d->tile_lo_n == 2 ? 1 : 2;
@@ -337,6 +338,12 @@ static int fill_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *co
 /* launches of the two forms of the 1024-point pass since the library was loaded (fftw_amd_p1024_launches) */
 static std::atomic<long long> g_p1024_full{0}, g_p1024_general{0};
 
+extern "C" int fftw_amd_p1024_tile_order(int order, long long nblocks, long long *place) {
+    if (nblocks < 1 || nblocks > 0x7fffffffLL || order < 0 || order >= FA_P1024_ORD_FORMS) return 0;
+    for (long long b = 0; place && b < nblocks; ++b) place[b] = (long long)p1024_order((unsigned)b, (unsigned)nblocks, order);
+    return FA_P1024_ORD_FORMS;
+}
+
 extern "C" void fftw_amd_p1024_launches(long long *full, long long *general) {
     if (full) *full = g_p1024_full.load();
     if (general) *general = g_p1024_general.load();
@@ -347,7 +354,7 @@ extern "C" void fftw_amd_p1024_launches(long long *full, long long *general) {
    31 bits on either side. */
 static bool p1024_full_ok(const P1024Args &pa, int tw) {
     if (tw == 1 || pa.lo_sh != 0 || pa.dn[0] % 8 != 0) return false;
-    if (pa.flags & ~(FFTW_AMD_F_NT_IN | FFTW_AMD_F_NT_OUT | FFTW_AMD_F_TW_IN)) return false;
+    if (pa.flags & ~(FFTW_AMD_F_NT_IN | FFTW_AMD_F_NT_OUT | FFTW_AMD_F_TW_IN | FFTW_AMD_F_P1024_EIGHTHS)) return false;
     const i64 lim = 0x7fffffffLL / 8 - 2;      /* in doubles */
     /* negative strides, and offsets that do not fit, keep the general kernel */
     if (pa.is_l <= 0 || pa.os_l <= 0 || pa.dis[0] < 0 || pa.dos[0] < 0) return false;
@@ -375,6 +382,10 @@ static int launch_p1024(const fftw_amd_step_desc *d, double *const *bufs, void *
     if (fill_p1024(d, bufs, tables, cs, cn, pa, &nblocks, &in_t, &out_t, &tw)) return 1;
     if (nblocks <= 0) return 0;
     const dim3 grid((unsigned)nblocks, 1, 1);
+    /* the skewed order goes to the passes whose input side is the strided one (the column pass of the two-pass plans:
+       128-byte segments at a row pitch on both sides); with contiguous rows on the input side no order measured a
+       gain over the eighths (profiles/r08_p1024_tile_order.txt) */
+    if (in_t && !(d->flags & FFTW_AMD_F_P1024_EIGHTHS)) pa.order = FA_P1024_ORD_SKEW;
     if (p1024_full_ok(pa, tw)) {
 #define FA_P1024_FULL(I, O, W) if (in_t == I && out_t == O && tw == W) { g_p1024_full.fetch_add(1); launch_p1024_full<I, O, W>(pa, grid, st); return 0; }
         FA_P1024_FULL(true, true, 0)   FA_P1024_FULL(true, true, 2)

@@ -314,13 +314,39 @@ struct P1024Args {
     int ndims, flags;
     int lo_sh;
     i64 lo_is, lo_os;
+    int order;            /* FA_P1024_ORD_* */
     long long *dbg;
 };
 
+/* Tile order of a launch: workgroup b of n -> place in the tile list (tile = place % ntiles, the loop dims from
+   place / ntiles).  Workgroups are dealt to the 8 XCDs round-robin, so x = b % 8 names the XCD and j = b / 8 counts its
+   workgroups in launch order.  A bijection of [0, n) for every n below 2^31 and either form, in 32-bit arithmetic
+   (j + rot < 2 e <= n / 4 + 2); tests/test_gpu_pass1024_order.py walks it on the CPU. */
+enum {
+    FA_P1024_ORD_EIGHTH = 0,    /* fa_xcd_remap: XCD x walks the x-th eighth of the list from its start (identity when n is
+                                   no multiple of 8) */
+    FA_P1024_ORD_SKEW = 1,      /* XCD x walks its eighth from x * (eighth / 8 | 1) tiles into it, wrapping round: in a launch
+                                   of 8 transforms of 128 tiles the XCDs otherwise walk 8 transforms in step, their streams
+                                   exact multiples of 16 MiB apart (profiles/r08_p1024_tile_order.txt) */
+    FA_P1024_ORD_FORMS = 2
+};
+__host__ __device__ inline unsigned p1024_order(unsigned b, unsigned n, int order) {
+    const unsigned x = b & 7, j = b >> 3, q = n >> 3, r = n & 7;
+    if (order == FA_P1024_ORD_SKEW) {
+        /* the eighths of a grid that is no multiple of 8 are unequal: XCD x owns e >= 1 tiles from s0 on */
+        const unsigned e = q + (x < r), s0 = x * q + (x < r ? x : r);
+        unsigned rot = x * ((e >> 3) | 1);
+        if (rot >= e) rot %= e;         /* short eighths only */
+        const unsigned p = j + rot;
+        return s0 + (p >= e ? p - e : p);
+    }
+    return r ? b : x * q + j;
+}
+
 /* this workgroup's tile of dim 0 and its offsets along the other loop dims; returns its place in the tile order */
 FA_DEV unsigned p1024_block_origin(const P1024Args &a, unsigned &tile, i64 &soff, i64 &doff, i64 &twb) {
-    unsigned blk = (unsigned)fa_xcd_remap((i64)blockIdx.x, (i64)gridDim.x);
     const unsigned nt = (unsigned)a.ntiles;
+    unsigned blk = p1024_order(blockIdx.x, gridDim.x, a.order);
     tile = blk % nt;
     unsigned rest = blk / nt;
     soff = 0; doff = 0; twb = 0;
@@ -343,7 +369,8 @@ pass1024_kernel(const P1024Args a) {
     if (ABL & 8) t_first = wall_clock64();
     /* workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8): give every XCD one
        contiguous eighth of the tile list, so that the 128-byte segments its CUs touch at
-       the same time are neighbours in memory (tests/micro/membw2.hip: +3...15 %) */
+       the same time are neighbours in memory (tests/micro/membw2.hip: +3...15 %); where in
+       its eighth an XCD starts is the launch's tile order (p1024_order) */
     /* the launcher keeps the grid below 2^31 blocks: 32-bit index arithmetic (a 64-bit
        division is ~130 instructions on this ISA, and this prologue is on every workgroup's
        critical path before its first load) */

@@ -94,7 +94,7 @@ fa_cfg fa_default_cfg(void) {
 /* The test switches (fa_knobs).  PRESENT: the int at `off` is 1 when the variable exists, whatever it holds -- the
    rule these hooks have always had.  LENS: the split that FFTW_AMD_FORCE_LENS="L1,L2,..." fixes for the axis whose
    length is the product (tests/test_gpu_menu.py reaches every kernel variant with it). */
-enum { KNOB_PRESENT, KNOB_LENS };
+enum { KNOB_PRESENT, KNOB_LENS, KNOB_P1024_ORDER };
 static const struct { const char *name; size_t off; int rule; } g_knob_table[] = {
     { "FFTW_AMD_NO_TUNED",       offsetof(fa_knobs, no_tuned),       KNOB_PRESENT },
     { "FFTW_AMD_NO_3S",          offsetof(fa_knobs, no_3s),          KNOB_PRESENT },
@@ -109,6 +109,7 @@ static const struct { const char *name; size_t off; int rule; } g_knob_table[] =
     { "FFTW_AMD_NO_RADIX4",      offsetof(fa_knobs, no_radix4),      KNOB_PRESENT },
     { "FFTW_AMD_FORCE_RADIX4",   offsetof(fa_knobs, force_radix4),   KNOB_PRESENT },
     { "FFTW_AMD_FORCE_LENS",     offsetof(fa_knobs, force_lens),     KNOB_LENS },
+    { "FFTW_AMD_P1024_ORDER",    offsetof(fa_knobs, p1024_order),    KNOB_P1024_ORDER },
 };
 
 static void fa_read_knobs(fa_knobs *k) {
@@ -118,6 +119,10 @@ static void fa_read_knobs(fa_knobs *k) {
         const char *c = getenv(g_knob_table[i].name);
         if (g_knob_table[i].rule == KNOB_PRESENT) {
             *(int *)((char *)k + g_knob_table[i].off) = c != NULL;
+            continue;
+        }
+        if (g_knob_table[i].rule == KNOB_P1024_ORDER) {
+            k->p1024_order = (c && atoi(c) >= 0) ? atoi(c) : FA_P1024_ORDER_DEFAULT;
             continue;
         }
         /* at most FA_MAXPASS entries are read (what follows them is not looked at); an entry below 1 or anything
@@ -520,6 +525,7 @@ static void emit_pass(plan *p, fa_loc src, fa_loc dst, i64 L, i64 is_l, i64 os_l
         if (L == 1024) {
             s->variant = FFTW_AMD_K_P1024;  /* register-resident radix-32x32, 8 sequences per tile */
             s->tile = 8;
+            if (p->knobs.p1024_order == 0) s->flags |= FFTW_AMD_F_P1024_EIGHTHS;
         } else if (L <= 32 && fa_hip_r1_tile((int)L) > 0 && is_l == 2 && os_l == 2 && tw_n == 0 && s->tile_lo_n == 1 &&
                    s->dim_is[0] == 2 * L && s->dim_os[0] == 2 * L && s->dim_n[0] >= 256 && !p->knobs.no_r1) {
             s->variant = FFTW_AMD_K_R1;     /* dense rows of a short length: one butterfly per row (pass1r.hpp) */

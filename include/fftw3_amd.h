@@ -435,6 +435,10 @@ enum {
                                       With pitch = n2 + 2 a volume occupies the same words on both sides and the step may run
                                       in place: every word of a volume is read before any is written.  The padding words of
                                       padded real rows are never written.  Planned only for aligned arrays */
+    FFTW_AMD_F_P1024_EIGHTHS = 1 << 21,/* pass of variant FFTW_AMD_K_P1024, set under FFTW_AMD_P1024_ORDER=0 only: every XCD walks
+                                      its eighth of a launch's tile list from the start in the column launches too (tile order
+                                      0 of fftw_amd_p1024_tile_order); without it XCD x starts x odd steps into its eighth
+                                      (order 1).  Which workgroup computes which tile, nothing else */
     FFTW_AMD_F_REAL_DEC_C2R = 1 << 17 /* pass: the FIRST trip of a two-trip c2r transform of n = L1 x L real points (pass3t_kernel,
                                       RD = 2), the backward twin of FFTW_AMD_F_REAL_DEC.  The source is the half spectrum
                                       X[0 ... n / 2], entry k at k1 dim_is[0] + k2 is_l for k = k1 + L1 k2 (so is_l = L1 dim_is[0]).
@@ -476,6 +480,11 @@ int fftw_amd_plan_lanes(const fftw_plan p);
    DEBUG / INTROSPECTION ONLY: a hook for the test suite and profiling scripts, not part of the stable ABI; it may
    change or go away without notice. */
 void fftw_amd_p1024_launches(long long *full, long long *general);
+/* The same kind of hook: place[b], b < nblocks, receives the place in the tile list (tile = place % tiles of the tile
+   dim, the loop dims from the quotient) that workgroup b of a launch of `nblocks` workgroups takes under tile order
+   `order`, evaluated on the host by the function the kernels call; place may be NULL.  Returns the number of orders the
+   library has (0 ... orders - 1), or 0 on arguments no launch has. */
+int fftw_amd_p1024_tile_order(int order, long long nblocks, long long *place);
 /* host copy of table `id` as interleaved doubles; returns its length in
    doubles (writes at most cap doubles). */
 long long fftw_amd_plan_table(const fftw_plan p, int id, double *dst, long long cap);
