@@ -69,6 +69,7 @@ F_P1024_EIGHTHS = 1 << 21
 K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D, K_IMG2DL, K_IMG2DR = range(12)
 K_VOL3D = 12
 K_VOL3DR = 13
+K_IMG2DLR = 14
 
 
 class StepDesc(C.Structure):
@@ -232,6 +233,7 @@ _sig("fftw_amd_factor_passes", C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_lon
 _sig("fa_hip_elem_form", C.c_int, C.POINTER(StepDesc), C.c_int, C.c_int, C.c_longlong)
 _sig("fa_hip_img2dl_tile", C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_img2dr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
+_sig("fa_hip_img2dlr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_lds", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("fa_hip_vol3dr_tile", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
@@ -281,6 +283,12 @@ def img2dr_tile(n0, n1, fwd=True):
     """images per workgroup of the one-trip real-image kernels (pass2dr.hpp, img2dr_menu.inc) for images of n0 rows x
     n1 real columns, r2c (fwd) or c2r; 0: the kernels do not cover that size.  Needs no device"""
     return int(lib.fa_hip_img2dr_tile(n0, n1, 1 if fwd else 0))
+
+
+def img2dlr_tile(n0, n1, fwd=True):
+    """images per workgroup of the one-trip real-image kernels for extents above 32 (pass2dlr.hpp, img2dlr_menu.inc) for
+    images of n0 rows x n1 real columns, r2c (fwd) or c2r; 0: the kernels do not cover that size.  Needs no device"""
+    return int(lib.fa_hip_img2dlr_tile(n0, n1, 1 if fwd else 0))
 
 
 def vol3d_tile(n0, n1, n2):

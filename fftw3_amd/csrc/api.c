@@ -190,10 +190,11 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
             int ci, pi, li, st, lf, rd, nl = (p->flags & (FFTW_PATIENT | FFTW_EXHAUSTIVE)) ? 2 : 1;
             /* r2c and c2r problems: also the two-trip plan decimated over the real data (cfg.real_dec, rd = 1) and the one-trip
                plan of small real images (cfg.real_img, rd = 2), each with the default chunking only; those of rank 3 also the
-               one-trip plan of small real volumes (cfg.real_vol, rd = 3), skipped when its plan lacks the step; c2c problems of rank 3
+               one-trip plan of small real volumes (cfg.real_vol, rd = 3), those of rank 2 the one-trip plan of real images with an
+               extent above 32 (cfg.real_imgl, rd = 3), both skipped when the plan is not the single step; c2c problems of rank 3
                likewise the one-trip plan of small volumes (cfg.vol3d, rd = 1), skipped when its plan lacks the step */
             const int real = (p->type == FA_R2C || p->type == FA_C2R);
-            const int nrd = real ? (p->rank == 3 ? 4 : 3) : ((p->type == FA_C2C && p->rank == 3) ? 2 : 1);
+            const int nrd = real ? ((p->rank == 3 || p->rank == 2) ? 4 : 3) : ((p->type == FA_C2C && p->rank == 3) ? 2 : 1);
             for (rd = 0; rd < nrd; ++rd)
             for (ci = 0; ci < 5; ++ci)
                 for (pi = 0; pi < 2; ++pi)
@@ -213,7 +214,8 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
                             c.real_dec = real && rd == 1;
                             c.real_img = real && rd == 2;
                             c.vol3d = !real && rd == 1;
-                            c.real_vol = real && rd == 3;
+                            c.real_vol = real && p->rank == 3 && rd == 3;
+                            c.real_imgl = real && p->rank == 2 && rd == 3;
                             q = clone_problem(p, c);
                             if (!q) continue;
                             /* the builder looks at the arrays (alignment, aliasing) */
@@ -222,6 +224,7 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
                             if (fa_build(q)) { fa_plan_free(q); continue; }
                             if (c.vol3d && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3D)) { fa_plan_free(q); continue; }
                             if (c.real_vol && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3DR)) { fa_plan_free(q); continue; }
+                            if (c.real_imgl && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_IMG2DLR)) { fa_plan_free(q); continue; }
                             q->in_lo = p->in_lo; q->in_hi = p->in_hi; q->out_lo = p->out_lo; q->out_hi = p->out_hi;
                             q->out_written = p->out_written;
                             fa_run(q, ri, ii, ro, io);          /* warm-up, device init */
@@ -807,7 +810,7 @@ void fftw_make_planner_thread_safe(void) {}
 
 /* ---- wisdom: text records "(key) chunk pipeline lmax bits ms", one per problem
    (bits: 1 = small_tiles, 2 = long_first, 4 | 8 = chunk lanes - 1, 16 = real_dec, 32 = real_img, 64 = vol3d,
-   128 = real_vol) */
+   128 = real_vol, 256 = real_imgl) */
 void fftw_forget_wisdom(void) {
     pthread_mutex_lock(&g_planner_lock);
     while (g_wisdom) { wis_entry *n = g_wisdom->next; free(g_wisdom); g_wisdom = n; }
@@ -826,7 +829,7 @@ char *fftw_export_wisdom_to_string(void) {
     len += (size_t)snprintf(s + len, cap - len, "(fftw3_amd_wisdom-1\n");
     for (w = g_wisdom; w; w = w->next)
         len += (size_t)snprintf(s + len, cap - len, "  (%s) %zu %d %d %d %.6f\n", w->key, w->cfg.chunk_bytes,
-                                w->cfg.pipeline, w->cfg.lmax_multi, (w->cfg.small_tiles ? 1 : 0) | (w->cfg.long_first ? 2 : 0) | (((w->cfg.lanes > 1 ? w->cfg.lanes - 1 : 0) & 3) << 2) | (w->cfg.real_dec ? 16 : 0) | (w->cfg.real_img ? 32 : 0) | (w->cfg.vol3d ? 64 : 0) | (w->cfg.real_vol ? 128 : 0), w->ms);
+                                w->cfg.pipeline, w->cfg.lmax_multi, (w->cfg.small_tiles ? 1 : 0) | (w->cfg.long_first ? 2 : 0) | (((w->cfg.lanes > 1 ? w->cfg.lanes - 1 : 0) & 3) << 2) | (w->cfg.real_dec ? 16 : 0) | (w->cfg.real_img ? 32 : 0) | (w->cfg.vol3d ? 64 : 0) | (w->cfg.real_vol ? 128 : 0) | (w->cfg.real_imgl ? 256 : 0), w->ms);
     snprintf(s + len, cap - len, ")\n");
     pthread_mutex_unlock(&g_planner_lock);
     return s;
@@ -874,7 +877,7 @@ int fftw_import_wisdom_from_string(const char *input) {
         w = (wis_entry *)calloc(1, sizeof(*w));
         if (!w) { ok = 0; break; }
         snprintf(w->key, sizeof(w->key), "%s", key);
-        w->cfg.chunk_bytes = chunk; w->cfg.pipeline = pipe != 0; w->cfg.lmax_multi = lmax; w->cfg.small_tiles = (small & 1) != 0; w->cfg.long_first = (small & 2) != 0; w->cfg.lanes = 1 + ((small >> 2) & 3); w->cfg.real_dec = (small & 16) != 0; w->cfg.real_img = (small & 32) != 0; w->cfg.vol3d = (small & 64) != 0; w->cfg.real_vol = (small & 128) != 0;
+        w->cfg.chunk_bytes = chunk; w->cfg.pipeline = pipe != 0; w->cfg.lmax_multi = lmax; w->cfg.small_tiles = (small & 1) != 0; w->cfg.long_first = (small & 2) != 0; w->cfg.lanes = 1 + ((small >> 2) & 3); w->cfg.real_dec = (small & 16) != 0; w->cfg.real_img = (small & 32) != 0; w->cfg.vol3d = (small & 64) != 0; w->cfg.real_vol = (small & 128) != 0; w->cfg.real_imgl = (small & 256) != 0;
         w->ms = ms;
         w->next = staged;
         staged = w;

@@ -76,6 +76,9 @@ typedef struct {
     int real_vol;         /* FFTW_AMD_REAL_VOL: batches of small 3-D r2c / c2r transforms in one trip (emit_real_volume,
                              FFTW_AMD_K_VOL3DR) instead of the axis-by-axis plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
                              candidate; a knob of its own, not implied by real_img */
+    int real_imgl;        /* FFTW_AMD_REAL_IMGL: batches of 2-D r2c / c2r transforms with extents up to 64, at least one above
+                             32, in one trip (emit_real_image, FFTW_AMD_K_IMG2DLR) instead of the axis-by-axis plans; off
+                             under FFTW_ESTIMATE, a FFTW_MEASURE candidate; a knob of its own, not implied by real_img */
 } fa_cfg;
 
 /* The planner's test switches, read from the environment by fa_read_knobs at the top of every fa_build (planner.c)

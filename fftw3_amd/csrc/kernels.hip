@@ -507,6 +507,12 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
         fprintf(stderr, "fftw3_amd: internal error: real-image step %d x %d with an unsupported layout\n", d->tile_lo_n, d->L);
         return -1;
     }
+    if (d->variant == FFTW_AMD_K_IMG2DLR) {
+        /* the same with an extent above 32 (kernels_imglr.hip) */
+        if (fa_launch_img2dlr(d, bufs, tables, cs, cn, st) == 0) return 0;
+        fprintf(stderr, "fftw3_amd: internal error: real-image step %d x %d with an unsupported layout\n", d->tile_lo_n, d->L);
+        return -1;
+    }
     if (d->variant == FFTW_AMD_K_VOL3D) {
         /* whole small volumes in one trip (kernels_vol.hip) */
         if (fa_launch_vol3d(d, bufs, tables, cs, cn, st) == 0) return 0;

@@ -134,6 +134,7 @@ int fa_launch_r2crows1(const fftw_amd_step_desc *d, double *const *bufs, void *c
 int fa_launch_img2d(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);    /* kernels_img.hip */
 int fa_launch_img2dl(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_imgl.hip */
 int fa_launch_img2dr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_imgr.hip */
+int fa_launch_img2dlr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);  /* kernels_imglr.hip */
 int fa_launch_vol3d(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);    /* kernels_vol.hip */
 int fa_launch_vol3dr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_volr.hip */
 /* kernels_sq.hip: FFTW_AMD_F_LO_DFT steps (rows + a DFT across the rows of a tile) */

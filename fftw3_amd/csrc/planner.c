@@ -65,6 +65,7 @@ fa_cfg fa_default_cfg(void) {
     c.real_img = 0;
     c.vol3d = 0;
     c.real_vol = 0;
+    c.real_imgl = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -86,6 +87,8 @@ fa_cfg fa_default_cfg(void) {
     if (e) c.vol3d = atoi(e) != 0;
     e = getenv("FFTW_AMD_REAL_VOL");
     if (e) c.real_vol = atoi(e) != 0;
+    e = getenv("FFTW_AMD_REAL_IMGL");
+    if (e) c.real_imgl = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
@@ -1864,18 +1867,26 @@ static int emit_r2c_axis(plan *p, i64 nl, const fa_axis *axp, fa_loc in, i64 rs,
    source of what the kernels cover.  Off under FFTW_ESTIMATE (cfg.real_img, FFTW_AMD_REAL_IMG=1): the numpy
    interpreter of the test suite's existing files does not know the step, and those files plan such problems with
    default settings; a candidate of the FFTW_MEASURE search for r2c / c2r problems, remembered by wisdom.
-   FFTW_AMD_NO_IMG2D=1 and FFTW_AMD_NO_TUNED=1 switch it off like the complex image steps.  1 = emitted. */
-static int emit_real_image(plan *p, int fwd) {
+   FFTW_AMD_NO_IMG2D=1 and FFTW_AMD_NO_TUNED=1 switch it off like the complex image steps.
+   variant FFTW_AMD_K_IMG2DLR (pass2dlr.hpp): the same step under the same layout rule for extents in {16, 32, 40, 48,
+   64} with at least one above 32, where the axis-by-axis plans make a real-row pass, the untangle / tangle and a
+   strided pass through a scratch buffer.  fa_hip_img2dlr_tile is the only source of what its kernels cover.  The
+   untangle / tangle twiddles are the stage table of the row axis (table, always), the intra-axis twiddles of a column
+   axis of two register stages that of the column axis (table2, n0 > 32).  A knob of its own (cfg.real_imgl,
+   FFTW_AMD_REAL_IMGL=1): existing tests plan 64 x 64 with FFTW_AMD_REAL_IMG=1 and interpret the plan with the base
+   numpy interpreter.  1 = emitted. */
+static int emit_real_image(plan *p, int fwd, int variant) {
     const fa_dim *col = &p->dims[0], *row = &p->dims[1];
     fftw_amd_step_desc *s;
     fa_loc in = { 0, 0, fwd ? 0 : p->in_im }, out = { 1, 0, fwd ? p->out_im : 0 };
     sdim d;
     i64 n0, n1, cp, rp, r_el, c_el, c_row, r_img, c_img;
     int T;
-    if (!p->cfg.real_img || p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
+    if (!(variant == FFTW_AMD_K_IMG2DR ? p->cfg.real_img : p->cfg.real_imgl)) return 0;
+    if (p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
     n0 = col->n; n1 = row->n;
-    if (n0 > 32 || n1 > 32) return 0;
-    T = fa_hip_img2dr_tile((int)n0, (int)n1, fwd);
+    if (n0 > 64 || n1 > 64) return 0;
+    T = (variant == FFTW_AMD_K_IMG2DR) ? fa_hip_img2dr_tile((int)n0, (int)n1, fwd) : fa_hip_img2dlr_tile((int)n0, (int)n1, fwd);
     if (T <= 0) return 0;
     cp = n1 + 2;
     r_el = fwd ? row->is : row->os; c_el = fwd ? row->os : row->is;
@@ -1900,7 +1911,11 @@ static int emit_real_image(plan *p, int fwd) {
     d.n = p->hrank ? p->chunk : 1; d.is = fwd ? r_img : c_img; d.os = fwd ? c_img : r_img; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
     step_set_dims(p, s, &d, 1, 0);
     s->tile = T;
-    s->variant = FFTW_AMD_K_IMG2DR;
+    s->variant = variant;
+    if (variant == FFTW_AMD_K_IMG2DLR) {
+        s->table = tab_stage(p, n1);
+        if (n0 > 32) s->table2 = tab_stage(p, n0);
+    }
     p->est_flops += 2.5 * (double)(n0 * n1) * (double)d.n * log2((double)(n0 * n1));
     return 1;
 }
@@ -1970,7 +1985,8 @@ static void build_r2c(plan *p) {
     i64 ext[FA_MAXRANK];
     fa_loc in = { 0, 0, 0 }, out = { 1, 0, p->out_im };
     fa_axis ax;
-    if (emit_real_image(p, 1)) return;
+    if (emit_real_image(p, 1, FFTW_AMD_K_IMG2DR)) return;
+    if (emit_real_image(p, 1, FFTW_AMD_K_IMG2DLR)) return;
     if (emit_real_volume(p, 1)) return;
     for (j = 0; j < r; ++j) ext[j] = p->dims[j].n;
     ext[r - 1] = half;
@@ -2150,7 +2166,8 @@ static void build_c2r(plan *p) {
     int cbuf = -1;
     fa_axis ax;
 
-    if (emit_real_image(p, 0)) return;
+    if (emit_real_image(p, 0, FFTW_AMD_K_IMG2DR)) return;
+    if (emit_real_image(p, 0, FFTW_AMD_K_IMG2DLR)) return;
     if (emit_real_volume(p, 0)) return;
     for (j = 0; j < r; ++j) { ext[j] = p->dims[j].n; cdims[j] = p->dims[j]; cdims[j].os = p->dims[j].is; }
     ext[r - 1] = half;
@@ -2609,6 +2626,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DR) sapp(s, cap, &len, "img2d-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_IMG2DLR) sapp(s, cap, &len, "img2dl-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_VOL3DR) sapp(s, cap, &len, "vol3d-%s-%dx%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", (int)d->aux_n, d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_VOL3D) sapp(s, cap, &len, "vol3d-%dx%dx%d", (int)d->aux_n, d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_BLUE) sapp(s, cap, &len, "bluestein-rows n=%lld", (long long)d->aux_n);

@@ -351,8 +351,15 @@ enum {
                                    (pass2dr.hpp); see the flag for the fields.  No fallback executor */
     FFTW_AMD_K_VOL3D = 12,      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_LO_DFT and FFTW_AMD_F_VOL3D: whole small volumes in one trip
                                    (pass3d.hpp); see FFTW_AMD_F_VOL3D for the fields.  No fallback executor */
-    FFTW_AMD_K_VOL3DR = 13      /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_VOL: whole small REAL volumes in one trip, r2c or c2r
+    FFTW_AMD_K_VOL3DR = 13,     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_VOL: whole small REAL volumes in one trip, r2c or c2r
                                    (pass3dr.hpp); see the flag for the fields.  No fallback executor */
+    FFTW_AMD_K_IMG2DLR = 14     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole REAL images with extents in {16, 32, 40, 48,
+                                   64} and at least one above 32 in one trip, r2c or c2r (pass2dlr.hpp).  The same transform and
+                                   every field as for FFTW_AMD_K_IMG2DR (see the flag), with two differences: `table` is the
+                                   stage table of the row axis (L entries (cos, sin)(2 pi m / L); the untangle / tangle reads
+                                   it) and is always present, `table2` is that of the column axis (tile_lo_n entries) and is
+                                   present exactly when tile_lo_n > 32 (an axis of two register stages), -1 otherwise.  The
+                                   plan owns these tables (16 bytes per entry) and no scratch buffer.  No fallback executor */
 };
 
 enum {
@@ -390,8 +397,9 @@ enum {
                                       before any write of the same word */
     FFTW_AMD_F_REAL_IMG  = 1 << 18,/* pass of variant FFTW_AMD_K_IMG2DR: the whole 2-D r2c (with FFTW_AMD_F_REAL_IN) or c2r (with
                                       FFTW_AMD_F_REAL_OUT) transform of real images of tile_lo_n = n0 rows x L = n1 real columns,
-                                      n1 even, both at most 32.  dims[0] is the loop over the images of the chunk, tile = images
-                                      per workgroup, tw_n = 0, table = table2 = -1, no swap flags.  The complex side is the
+                                      n1 even, both at most 32 (variant FFTW_AMD_K_IMG2DLR: the same step for extents up to 64,
+                                      with the stage tables described there).  dims[0] is the loop over the images of the chunk,
+                                      tile = images per workgroup, tw_n = 0, table = table2 = -1, no swap flags.  The complex side is the
                                       dense half spectrum: n0 rows of n1 / 2 + 1 interleaved entries (im = 1, entries 2 apart,
                                       rows n1 + 2 doubles apart, images n0 (n1 + 2) apart); the real side has im = 0, elements 1
                                       apart, rows `pitch` = n1 or n1 + 2 doubles apart and images n0 pitch apart.
