@@ -9,7 +9,7 @@ LIBDIR := fftw3_amd/lib
 CFLAGS := -O2 -fPIC -std=gnu99 -Wall -Wextra -Iinclude -I$(CSRC)
 HIPFLAGS := -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -std=c++17 -Wall
 
-OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/split.o $(CSRC)/exec.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgr.o $(CSRC)/kernels_imglr.o $(CSRC)/kernels_vol.o $(CSRC)/kernels_volr.o
+OBJS := $(CSRC)/api.o $(CSRC)/planner.o $(CSRC)/split.o $(CSRC)/exec.o $(CSRC)/sharded.o $(CSRC)/slab.o $(CSRC)/slab1d.o $(CSRC)/hostmath.o $(CSRC)/kernels.o $(CSRC)/kernels_elem.o $(CSRC)/fa_hip.o $(CSRC)/kernels_rr.o $(CSRC)/kernels_rr1.o $(CSRC)/kernels_rr2.o $(CSRC)/kernels_r3.o $(CSRC)/kernels_r3r.o $(CSRC)/kernels_r2cm.o $(CSRC)/kernels_blue.o $(CSRC)/kernels_r1.o $(CSRC)/kernels_sq.o $(CSRC)/kernels_r3w.o $(CSRC)/kernels_r3tw.o $(CSRC)/kernels_bluew.o $(CSRC)/kernels_slab.o $(CSRC)/kernels_tr.o $(CSRC)/kernels_img.o $(CSRC)/kernels_imgl.o $(CSRC)/kernels_imgw.o $(CSRC)/kernels_imgr.o $(CSRC)/kernels_imglr.o $(CSRC)/kernels_vol.o $(CSRC)/kernels_volr.o
 
 all: $(LIBDIR)/libfftw3_amd.so
 
@@ -66,6 +66,9 @@ $(CSRC)/kernels_img.o: $(CSRC)/kernels_img.hip $(HIPCOMMON) $(CSRC)/passrr.hpp $
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/kernels_imgl.o: $(CSRC)/kernels_imgl.hip $(HIPCOMMON) $(CSRC)/passrr.hpp $(CSRC)/pass2d.hpp $(CSRC)/pass2dl.hpp $(CSRC)/img2dl_menu.inc
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/kernels_imgw.o: $(CSRC)/kernels_imgw.hip $(HIPCOMMON) $(CSRC)/passrr.hpp $(CSRC)/pass2d.hpp $(CSRC)/pass2dl.hpp $(CSRC)/pass2dw.hpp $(CSRC)/img2dw_menu.inc
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/kernels_imgr.o: $(CSRC)/kernels_imgr.hip $(HIPCOMMON) $(CSRC)/passrr.hpp $(CSRC)/pass2d.hpp $(CSRC)/pass2dr.hpp $(CSRC)/img2dr_menu.inc

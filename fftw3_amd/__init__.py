@@ -70,6 +70,7 @@ K_GENERIC, K_P1024, K_RR, K_R3, K_R2C, K_C2R, K_R1, K_BLUE, K_TRANSPOSE, K_IMG2D
 K_VOL3D = 12
 K_VOL3DR = 13
 K_IMG2DLR = 14
+K_IMG2DW = 15
 
 
 class StepDesc(C.Structure):
@@ -232,6 +233,7 @@ _sig("fftw_amd_power_mod", C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlon
 _sig("fftw_amd_factor_passes", C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_longlong))
 _sig("fa_hip_elem_form", C.c_int, C.POINTER(StepDesc), C.c_int, C.c_int, C.c_longlong)
 _sig("fa_hip_img2dl_tile", C.c_int, C.c_int, C.c_int)
+_sig("fa_hip_img2dw_tile", C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_img2dr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_img2dlr_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_tile", C.c_int, C.c_int, C.c_int, C.c_int)
@@ -277,6 +279,12 @@ def img2dl_tile(n0, n1):
     """images per workgroup of the one-trip image kernel for extents above 32 (pass2dl.hpp, img2dl_menu.inc) for images
     of n0 rows x n1 columns; 0: the kernel does not cover that size.  Needs no device"""
     return int(lib.fa_hip_img2dl_tile(n0, n1))
+
+
+def img2dw_tile(n0, n1):
+    """images per workgroup of the one-trip image kernel for an extent of 128 (pass2dw.hpp, img2dw_menu.inc) for images
+    of n0 rows x n1 columns; 0: the kernel does not cover that size.  Needs no device"""
+    return int(lib.fa_hip_img2dw_tile(n0, n1))
 
 
 def img2dr_tile(n0, n1, fwd=True):

@@ -96,6 +96,14 @@ static double now_ms(void) {
     return 1e3 * (double)ts.tv_sec + 1e-6 * (double)ts.tv_nsec;
 }
 
+/* the two steps of emit_vol_planes (planner.c): an image step over the planes, then one pass of the first axis */
+static int fa_is_planes_plan(const plan *q) {
+    const fftw_amd_step_desc *s = q->steps;
+    return q->nsteps == 2 && s[0].kind == FFTW_AMD_STEP_PASS && (s[0].flags & FFTW_AMD_F_LO_DFT) && s[0].batch_dim < 0 &&
+           (s[0].variant == FFTW_AMD_K_IMG2D || s[0].variant == FFTW_AMD_K_IMG2DL || s[0].variant == FFTW_AMD_K_IMG2DW) &&
+           s[1].kind == FFTW_AMD_STEP_PASS && s[1].src_buf == 1 && s[1].dst_buf == 1;
+}
+
 /* copy the problem description of `p` into a fresh plan with configuration c */
 static plan *clone_problem(const plan *p, fa_cfg c) {
     plan *q = fa_plan_new();
@@ -192,9 +200,12 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
                plan of small real images (cfg.real_img, rd = 2), each with the default chunking only; those of rank 3 also the
                one-trip plan of small real volumes (cfg.real_vol, rd = 3), those of rank 2 the one-trip plan of real images with an
                extent above 32 (cfg.real_imgl, rd = 3), both skipped when the plan is not the single step; c2c problems of rank 3
-               likewise the one-trip plan of small volumes (cfg.vol3d, rd = 1), skipped when its plan lacks the step */
+               likewise the one-trip plan of small volumes (cfg.vol3d, rd = 1), skipped when its plan lacks the step, and the
+               two-trip planes plan (cfg.vol_planes, rd = 2), skipped when its plan is not the image step and one pass; c2c
+               problems of rank 2 the one-trip plan of images with an extent of 128 (cfg.img_wide, rd = 1), skipped when its
+               plan is not the single step */
             const int real = (p->type == FA_R2C || p->type == FA_C2R);
-            const int nrd = real ? ((p->rank == 3 || p->rank == 2) ? 4 : 3) : ((p->type == FA_C2C && p->rank == 3) ? 2 : 1);
+            const int nrd = real ? ((p->rank == 3 || p->rank == 2) ? 4 : 3) : ((p->type == FA_C2C && p->rank == 3) ? 3 : ((p->type == FA_C2C && p->rank == 2) ? 2 : 1));
             for (rd = 0; rd < nrd; ++rd)
             for (ci = 0; ci < 5; ++ci)
                 for (pi = 0; pi < 2; ++pi)
@@ -213,7 +224,9 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
                             c.long_first = lf;
                             c.real_dec = real && rd == 1;
                             c.real_img = real && rd == 2;
-                            c.vol3d = !real && rd == 1;
+                            c.vol3d = !real && p->rank == 3 && rd == 1;
+                            c.vol_planes = !real && p->rank == 3 && rd == 2;
+                            c.img_wide = !real && p->rank == 2 && rd == 1;
                             c.real_vol = real && p->rank == 3 && rd == 3;
                             c.real_imgl = real && p->rank == 2 && rd == 3;
                             q = clone_problem(p, c);
@@ -223,6 +236,8 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
                             q->inplace = p->inplace;
                             if (fa_build(q)) { fa_plan_free(q); continue; }
                             if (c.vol3d && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3D)) { fa_plan_free(q); continue; }
+                            if (c.vol_planes && !fa_is_planes_plan(q)) { fa_plan_free(q); continue; }
+                            if (c.img_wide && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_IMG2DW)) { fa_plan_free(q); continue; }
                             if (c.real_vol && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3DR)) { fa_plan_free(q); continue; }
                             if (c.real_imgl && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_IMG2DLR)) { fa_plan_free(q); continue; }
                             q->in_lo = p->in_lo; q->in_hi = p->in_hi; q->out_lo = p->out_lo; q->out_hi = p->out_hi;
@@ -810,7 +825,7 @@ void fftw_make_planner_thread_safe(void) {}
 
 /* ---- wisdom: text records "(key) chunk pipeline lmax bits ms", one per problem
    (bits: 1 = small_tiles, 2 = long_first, 4 | 8 = chunk lanes - 1, 16 = real_dec, 32 = real_img, 64 = vol3d,
-   128 = real_vol, 256 = real_imgl) */
+   128 = real_vol, 256 = real_imgl, 512 = vol_planes, 1024 = img_wide) */
 void fftw_forget_wisdom(void) {
     pthread_mutex_lock(&g_planner_lock);
     while (g_wisdom) { wis_entry *n = g_wisdom->next; free(g_wisdom); g_wisdom = n; }
@@ -829,7 +844,7 @@ char *fftw_export_wisdom_to_string(void) {
     len += (size_t)snprintf(s + len, cap - len, "(fftw3_amd_wisdom-1\n");
     for (w = g_wisdom; w; w = w->next)
         len += (size_t)snprintf(s + len, cap - len, "  (%s) %zu %d %d %d %.6f\n", w->key, w->cfg.chunk_bytes,
-                                w->cfg.pipeline, w->cfg.lmax_multi, (w->cfg.small_tiles ? 1 : 0) | (w->cfg.long_first ? 2 : 0) | (((w->cfg.lanes > 1 ? w->cfg.lanes - 1 : 0) & 3) << 2) | (w->cfg.real_dec ? 16 : 0) | (w->cfg.real_img ? 32 : 0) | (w->cfg.vol3d ? 64 : 0) | (w->cfg.real_vol ? 128 : 0) | (w->cfg.real_imgl ? 256 : 0), w->ms);
+                                w->cfg.pipeline, w->cfg.lmax_multi, (w->cfg.small_tiles ? 1 : 0) | (w->cfg.long_first ? 2 : 0) | (((w->cfg.lanes > 1 ? w->cfg.lanes - 1 : 0) & 3) << 2) | (w->cfg.real_dec ? 16 : 0) | (w->cfg.real_img ? 32 : 0) | (w->cfg.vol3d ? 64 : 0) | (w->cfg.real_vol ? 128 : 0) | (w->cfg.real_imgl ? 256 : 0) | (w->cfg.vol_planes ? 512 : 0) | (w->cfg.img_wide ? 1024 : 0), w->ms);
     snprintf(s + len, cap - len, ")\n");
     pthread_mutex_unlock(&g_planner_lock);
     return s;
@@ -877,7 +892,7 @@ int fftw_import_wisdom_from_string(const char *input) {
         w = (wis_entry *)calloc(1, sizeof(*w));
         if (!w) { ok = 0; break; }
         snprintf(w->key, sizeof(w->key), "%s", key);
-        w->cfg.chunk_bytes = chunk; w->cfg.pipeline = pipe != 0; w->cfg.lmax_multi = lmax; w->cfg.small_tiles = (small & 1) != 0; w->cfg.long_first = (small & 2) != 0; w->cfg.lanes = 1 + ((small >> 2) & 3); w->cfg.real_dec = (small & 16) != 0; w->cfg.real_img = (small & 32) != 0; w->cfg.vol3d = (small & 64) != 0; w->cfg.real_vol = (small & 128) != 0; w->cfg.real_imgl = (small & 256) != 0;
+        w->cfg.chunk_bytes = chunk; w->cfg.pipeline = pipe != 0; w->cfg.lmax_multi = lmax; w->cfg.small_tiles = (small & 1) != 0; w->cfg.long_first = (small & 2) != 0; w->cfg.lanes = 1 + ((small >> 2) & 3); w->cfg.real_dec = (small & 16) != 0; w->cfg.real_img = (small & 32) != 0; w->cfg.vol3d = (small & 64) != 0; w->cfg.real_vol = (small & 128) != 0; w->cfg.real_imgl = (small & 256) != 0; w->cfg.vol_planes = (small & 512) != 0; w->cfg.img_wide = (small & 1024) != 0;
         w->ms = ms;
         w->next = staged;
         staged = w;

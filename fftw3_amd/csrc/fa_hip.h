@@ -29,6 +29,7 @@ int   fa_hip_blue_tile(int nb);  /* its rows per tile */
 int   fa_hip_r1_tile(int L);   /* rows per tile of the one-stage rows kernel (L = 2 ... 32), 0: none */
 int   fa_hip_img2d_tile(int n0, int n1);  /* images per tile of the one-trip small-image kernel (img2d_menu.inc), 0: none */
 int   fa_hip_img2dl_tile(int n0, int n1); /* the same for the kernel of extents above 32 (img2dl_menu.inc), 0: none */
+int   fa_hip_img2dw_tile(int n0, int n1); /* the same for the 512-item kernel of an extent of 128 (img2dw_menu.inc), 0: none */
 int   fa_hip_img2dr_tile(int n0, int n1, int fwd); /* ... of the small real-image kernels, r2c (fwd) or c2r (img2dr_menu.inc), 0: none */
 int   fa_hip_img2dlr_tile(int n0, int n1, int fwd); /* ... of the real-image kernels of extents above 32, r2c (fwd) or c2r (img2dlr_menu.inc), 0: none */
 int   fa_hip_vol3d_tile(int n0, int n1, int n2);   /* volumes per tile of the one-trip small-volume kernel (vol3d_menu.inc), 0: none */

@@ -79,6 +79,12 @@ typedef struct {
     int real_imgl;        /* FFTW_AMD_REAL_IMGL: batches of 2-D r2c / c2r transforms with extents up to 64, at least one above
                              32, in one trip (emit_real_image, FFTW_AMD_K_IMG2DLR) instead of the axis-by-axis plans; off
                              under FFTW_ESTIMATE, a FFTW_MEASURE candidate; a knob of its own, not implied by real_img */
+    int vol_planes;       /* FFTW_AMD_VOL_PLANES: dense 3-D c2c volumes in two trips, the (n1, n2) planes as one image step and
+                             the first axis as one pass in place on the output (emit_vol_planes), instead of one trip per
+                             axis; off under FFTW_ESTIMATE, a FFTW_MEASURE candidate */
+    int img_wide;         /* FFTW_AMD_IMG_WIDE: batches of 2-D c2c transforms 128 x 128, 64 x 128 and 128 x 64 in one trip
+                             (emit_images, FFTW_AMD_K_IMG2DW) instead of the two-trip plans; off under FFTW_ESTIMATE, a
+                             FFTW_MEASURE candidate.  Not needed for the planes of a vol_planes plan */
 } fa_cfg;
 
 /* The planner's test switches, read from the environment by fa_read_knobs at the top of every fa_build (planner.c)

@@ -501,6 +501,12 @@ static int launch_pass(const fftw_amd_step_desc *d, double *const *bufs, void *c
         fprintf(stderr, "fftw3_amd: internal error: image step %d x %d with an unsupported layout\n", d->tile_lo_n, d->L);
         return -1;
     }
+    if (d->variant == FFTW_AMD_K_IMG2DW) {
+        /* the same with an extent of 128, one tile per 512-item workgroup (kernels_imgw.hip) */
+        if (fa_launch_img2dw(d, bufs, tables, cs, cn, st) == 0) return 0;
+        fprintf(stderr, "fftw3_amd: internal error: wide-image step %d x %d with an unsupported layout\n", d->tile_lo_n, d->L);
+        return -1;
+    }
     if (d->variant == FFTW_AMD_K_IMG2DR) {
         /* whole small real images, r2c or c2r (kernels_imgr.hip) */
         if (fa_launch_img2dr(d, bufs, tables, cs, cn, st) == 0) return 0;

@@ -133,6 +133,7 @@ int fa_launch_pass1r(const fftw_amd_step_desc *d, double *const *bufs, void *con
 int fa_launch_r2crows1(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);
 int fa_launch_img2d(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);    /* kernels_img.hip */
 int fa_launch_img2dl(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_imgl.hip */
+int fa_launch_img2dw(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_imgw.hip */
 int fa_launch_img2dr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);   /* kernels_imgr.hip */
 int fa_launch_img2dlr(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);  /* kernels_imglr.hip */
 int fa_launch_vol3d(const fftw_amd_step_desc *d, double *const *bufs, void *const *tables, i64 cs, i64 cn, hipStream_t st);    /* kernels_vol.hip */

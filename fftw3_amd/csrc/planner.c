@@ -66,6 +66,8 @@ fa_cfg fa_default_cfg(void) {
     c.vol3d = 0;
     c.real_vol = 0;
     c.real_imgl = 0;
+    c.vol_planes = 0;
+    c.img_wide = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -89,6 +91,10 @@ fa_cfg fa_default_cfg(void) {
     if (e) c.real_vol = atoi(e) != 0;
     e = getenv("FFTW_AMD_REAL_IMGL");
     if (e) c.real_imgl = atoi(e) != 0;
+    e = getenv("FFTW_AMD_VOL_PLANES");
+    if (e) c.vol_planes = atoi(e) != 0;
+    e = getenv("FFTW_AMD_IMG_WIDE");
+    if (e) c.img_wide = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
     return c;
@@ -1249,24 +1255,27 @@ static int emit_rows_lo_dft(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_ou
    images, at most one howmany loop (mk_guru drops the extent-1 ones) that steps over exactly one image on both sides,
    16-byte aligned arrays, no FFTW_UNALIGNED.  No scratch, in place or out of place.  fa_hip_img2d_tile and
    fa_hip_img2dl_tile are the only sources of what the kernels cover.  FFTW_AMD_NO_IMG2D=1 (no whole images in one
-   trip) restores the two-trip plans for both.  1 = emitted. */
-static int emit_images(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, int variant) {
-    const fa_dim *col = &p->dims[0], *row = &p->dims[1];
+   trip) restores the two-trip plans for both.  A third family, off under FFTW_ESTIMATE (cfg.img_wide,
+   FFTW_AMD_IMG_WIDE=1, a FFTW_MEASURE candidate): 128 x 128, 64 x 128 and 128 x 64, a pair of img2dw_menu.inc, one tile
+   of 16384 elements per 512-item workgroup (FFTW_AMD_K_IMG2DW, pass2dw.hpp; both axes two stages, both tables; its
+   tile query is fa_hip_img2dw_tile), under the same layout rule and the same two switches.  emit_images, below its
+   two helpers: 1 = emitted. */
+
+/* images per tile of a family's kernel for n0 x n1 (0: none) */
+static int image_tile(int variant, i64 n0, i64 n1) {
+    if (n0 > 128 || n1 > 128) return 0;
+    if (variant == FFTW_AMD_K_IMG2D) return fa_hip_img2d_tile((int)n0, (int)n1);
+    if (variant == FFTW_AMD_K_IMG2DL) return fa_hip_img2dl_tile((int)n0, (int)n1);
+    return fa_hip_img2dw_tile((int)n0, (int)n1);
+}
+
+/* the step itself: nimg dense images n0 x n1 one after another, T per workgroup; the loop over them is the batch
+   loop of the plan (is_batch) or a loop of its own */
+static int emit_image_step(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, int variant, i64 n0, i64 n1, int T,
+                           i64 nimg, int is_batch) {
+    const i64 img = 2 * n0 * n1;
     fftw_amd_step_desc *s;
     sdim d;
-    i64 n0, n1, img;
-    int T;
-    if (p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
-    n0 = col->n; n1 = row->n;
-    if (n0 > 64 || n1 > 64) return 0;
-    T = (variant == FFTW_AMD_K_IMG2D) ? fa_hip_img2d_tile((int)n0, (int)n1) : fa_hip_img2dl_tile((int)n0, (int)n1);
-    if (T <= 0) return 0;
-    img = 2 * n0 * n1;
-    if (in.im != 1 || out.im != 1) return 0;
-    if (row->is != 2 || row->os != 2 || col->is != 2 * n1 || col->os != 2 * n1) return 0;
-    if (p->hrank && (p->hdims[0].is != img || p->hdims[0].os != img)) return 0;
-    if (p->flags & FFTW_UNALIGNED) return 0;
-    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
     s = new_step(p, FFTW_AMD_STEP_PASS);
     step_set_locs(s, in, out);
     s->flags = sw_in | sw_out | FFTW_AMD_F_LO_DFT;
@@ -1278,16 +1287,34 @@ static int emit_images(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, in
     s->tile_lo_n = (int)n0;
     s->tile_lo_is = 2 * n1;
     s->tile_lo_os = 2 * n1;
-    d.n = p->hrank ? p->chunk : 1; d.is = img; d.os = img; d.tw = 0; d.is_batch = p->hrank ? 1 : 0;
+    d.n = nimg; d.is = img; d.os = img; d.tw = 0; d.is_batch = is_batch;
     step_set_dims(p, s, &d, 1, 0);
     s->tile = T;
     s->variant = variant;
-    if (variant == FFTW_AMD_K_IMG2DL) {
+    if (variant != FFTW_AMD_K_IMG2D) {
         if (n1 > 32) s->table = tab_stage(p, n1);
         if (n0 > 32) s->table2 = tab_stage(p, n0);
     }
     p->est_flops += 5.0 * (double)(n0 * n1) * (double)d.n * log2((double)(n0 * n1));
     return 1;
+}
+
+static int emit_images(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out, int variant) {
+    const fa_dim *col = &p->dims[0], *row = &p->dims[1];
+    i64 n0, n1, img;
+    int T;
+    if (p->rank != 2 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
+    if (variant == FFTW_AMD_K_IMG2DW && !p->cfg.img_wide) return 0;
+    n0 = col->n; n1 = row->n;
+    T = image_tile(variant, n0, n1);
+    if (T <= 0) return 0;
+    img = 2 * n0 * n1;
+    if (in.im != 1 || out.im != 1) return 0;
+    if (row->is != 2 || row->os != 2 || col->is != 2 * n1 || col->os != 2 * n1) return 0;
+    if (p->hrank && (p->hdims[0].is != img || p->hdims[0].os != img)) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    return emit_image_step(p, in, out, sw_in, sw_out, variant, n0, n1, T, p->hrank ? p->chunk : 1, p->hrank ? 1 : 0);
 }
 
 static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
@@ -1296,6 +1323,10 @@ static int emit_img2d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
 
 static int emit_img2dl(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     return emit_images(p, in, out, sw_in, sw_out, FFTW_AMD_K_IMG2DL);
+}
+
+static int emit_img2dw(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    return emit_images(p, in, out, sw_in, sw_out, FFTW_AMD_K_IMG2DW);
 }
 
 /* A batch of small three-dimensional transforms n0 x n1 x n2 on dense contiguous volumes, in ONE trip
@@ -1341,6 +1372,52 @@ static int emit_vol3d(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
     s->tile = T;
     s->variant = FFTW_AMD_K_VOL3D;
     p->est_flops += 5.0 * (double)(n0 * n1 * n2) * (double)d.n * log2((double)(n0 * n1 * n2));
+    return 1;
+}
+
+/* A batch of three-dimensional transforms n0 x n1 x n2 on dense contiguous volumes in TWO trips where the
+   axis-by-axis plan crosses HBM three times: the (n1, n2) planes of the chunk's volumes are one run of chunk x n0
+   dense images, which one image step (FFTW_AMD_K_IMG2D, _IMG2DL or _IMG2DW, whichever tile query takes the pair)
+   transforms from `in` to `out`; the first axis is then one strided pass in place on `out` through the axis emitter,
+   its loops the n1 n2 contiguous columns and the batch.  The image step has no other executor, so everything it needs
+   is settled here (the conditions of emit_vol3d), and whether n0 is ONE pass is decided before anything is emitted:
+   in every other case the plan of the axis loop is built, step for step.  The loop over the planes is no batch dim: it
+   counts planes, not volumes, and the plan -- the caller's two arrays, no scratch -- runs in one chunk
+   (fa_build_steps_sized).  No scratch, in place or out of place.  Off under FFTW_ESTIMATE (cfg.vol_planes,
+   FFTW_AMD_VOL_PLANES=1), a FFTW_MEASURE candidate, for the reason given at emit_vol3d; FFTW_AMD_NO_IMG2D=1 and
+   FFTW_AMD_NO_TUNED=1 switch it off like the image steps.  1 = emitted. */
+static int emit_vol_planes(plan *p, fa_loc in, fa_loc out, int sw_in, int sw_out) {
+    static const int families[3] = { FFTW_AMD_K_IMG2D, FFTW_AMD_K_IMG2DL, FFTW_AMD_K_IMG2DW };
+    const fa_dim *d0 = &p->dims[0], *d1 = &p->dims[1], *d2 = &p->dims[2];
+    const i64 chunk = p->hrank ? p->chunk : 1;
+    i64 n0, n1, n2, vol, lens[FA_MAXPASS];
+    fa_axis ax;
+    int f, T = 0, variant = 0;
+    if (!p->cfg.vol_planes || p->rank != 3 || p->hrank > 1 || p->knobs.no_tuned || p->knobs.no_img2d) return 0;
+    if (in.buf != 0 || out.buf != 1) return 0;
+    n0 = d0->n; n1 = d1->n; n2 = d2->n;
+    for (f = 0; f < 3 && T <= 0; ++f) { variant = families[f]; T = image_tile(variant, n1, n2); }
+    if (T <= 0) return 0;
+    vol = 2 * n0 * n1 * n2;
+    if (in.im != 1 || out.im != 1) return 0;
+    if (d2->is != 2 || d2->os != 2 || d1->is != 2 * n2 || d1->os != 2 * n2 || d0->is != 2 * n1 * n2 || d0->os != 2 * n1 * n2) return 0;
+    if (p->hrank && (p->hdims[0].is != vol || p->hdims[0].os != vol)) return 0;
+    if (p->flags & FFTW_UNALIGNED) return 0;
+    if (((size_t)p->ri % 16) || ((size_t)p->ro % 16)) return 0;
+    /* the first axis, in place on the output */
+    memset(&ax, 0, sizeof(ax));
+    ax.n = n0;
+    ax.is = d0->os;
+    ax.os = d0->os;
+    ax.src = out;
+    ax.dst = out;
+    ax.flags_in = sw_in;
+    ax.flags_out = sw_out;
+    if (collect_loops(p, p->dims, p->rank, 0, NULL, 1, &ax)) return 0;
+    if (!fa_lds_able(n0) || axis_split(p, &ax, 0, lens) != 1) return 0;
+    emit_image_step(p, in, out, sw_in, sw_out, variant, n1, n2, T, chunk * n0, 0);
+    if (p->failed) return 1;
+    fa_emit_axis(p, &ax);
     return 1;
 }
 
@@ -1455,7 +1532,9 @@ static void build_c2c_on(plan *p, fa_loc in, fa_loc out) {
     if (emit_rows_lo_dft(p, in, out, sw_in, sw_out)) return;
     if (emit_img2d(p, in, out, sw_in, sw_out)) return;
     if (emit_img2dl(p, in, out, sw_in, sw_out)) return;
+    if (emit_img2dw(p, in, out, sw_in, sw_out)) return;
     if (emit_vol3d(p, in, out, sw_in, sw_out)) return;
+    if (emit_vol_planes(p, in, out, sw_in, sw_out)) return;
     for (a = p->rank - 1; a >= 0; --a) {
         fa_axis ax;
         memset(&ax, 0, sizeof(ax));
@@ -2625,6 +2704,7 @@ char *fa_sprint(const plan *p) {
             else if (d->variant == FFTW_AMD_K_R1) sapp(s, cap, &len, "reg1");
             else if (d->variant == FFTW_AMD_K_IMG2D) sapp(s, cap, &len, "img2d-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DL) sapp(s, cap, &len, "img2dl-%dx%d", d->tile_lo_n, d->L);
+            else if (d->variant == FFTW_AMD_K_IMG2DW) sapp(s, cap, &len, "img2dw-%dx%d", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DR) sapp(s, cap, &len, "img2d-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_IMG2DLR) sapp(s, cap, &len, "img2dl-%s-%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", d->tile_lo_n, d->L);
             else if (d->variant == FFTW_AMD_K_VOL3DR) sapp(s, cap, &len, "vol3d-%s-%dx%dx%d", (d->flags & FFTW_AMD_F_REAL_IN) ? "r2c" : "c2r", (int)d->aux_n, d->tile_lo_n, d->L);

@@ -353,13 +353,20 @@ enum {
                                    (pass3d.hpp); see FFTW_AMD_F_VOL3D for the fields.  No fallback executor */
     FFTW_AMD_K_VOL3DR = 13,     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_VOL: whole small REAL volumes in one trip, r2c or c2r
                                    (pass3dr.hpp); see the flag for the fields.  No fallback executor */
-    FFTW_AMD_K_IMG2DLR = 14     /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole REAL images with extents in {16, 32, 40, 48,
+    FFTW_AMD_K_IMG2DLR = 14,    /* FFTW_AMD_STEP_PASS with FFTW_AMD_F_REAL_IMG: whole REAL images with extents in {16, 32, 40, 48,
                                    64} and at least one above 32 in one trip, r2c or c2r (pass2dlr.hpp).  The same transform and
                                    every field as for FFTW_AMD_K_IMG2DR (see the flag), with two differences: `table` is the
                                    stage table of the row axis (L entries (cos, sin)(2 pi m / L); the untangle / tangle reads
                                    it) and is always present, `table2` is that of the column axis (tile_lo_n entries) and is
                                    present exactly when tile_lo_n > 32 (an axis of two register stages), -1 otherwise.  The
                                    plan owns these tables (16 bytes per entry) and no scratch buffer.  No fallback executor */
+    FFTW_AMD_K_IMG2DW = 15      /* the FFTW_AMD_K_IMG2DL step (every field as for FFTW_AMD_K_IMG2D) for 128 x 128, 64 x 128 and
+                                   128 x 64 images (pass2dw.hpp, 512 work-items per tile of 16384 elements): both axes are two
+                                   register stages, so `table` (row axis, L entries) and `table2` (column axis, tile_lo_n
+                                   entries) are both present.  In the planes plan of a rank-3 problem (the (n1, n2) planes in
+                                   one trip, then the first axis in place on the output) the image step of any of the three
+                                   families has dims[0] = the chunk's n0 planes per volume x volumes, and is no batch dim
+                                   (batch_dim = -1): the plan has no scratch, so it runs in one chunk */
 };
 
 enum {
