@@ -240,6 +240,7 @@ _sig("fa_hip_vol3d_tile", C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3d_lds", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("fa_hip_vol3dr_tile", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
 _sig("fa_hip_vol3dr_lds", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int))
+_sig("fa_measure_candidates_text", C.c_int, C.c_int, C.c_int, C.c_uint, C.c_char_p, C.c_size_t)
 _libc_free = C.CDLL(None).free
 _libc_free.argtypes = [_vp]
 
@@ -309,6 +310,14 @@ def vol3dr_tile(n0, n1, n2, fwd=True):
     """volumes per workgroup of the one-trip real-volume kernels (pass3dr.hpp, vol3dr_menu.inc) for row-major volumes of
     n0 x n1 x n2 reals, r2c (fwd) or c2r; 0: the kernels do not cover that size.  Needs no device"""
     return int(lib.fa_hip_vol3dr_tile(n0, n1, n2, 1 if fwd else 0))
+
+
+def measure_candidates(ptype, rank, flags):
+    """the configurations the FFTW_MEASURE search times for a problem of type ptype (0 c2c, 1 r2c, 2 c2r, 3 r2r) and
+    rank, in its order: one "chunk pipeline lmax bits" string each, the integers of a wisdom record.  Needs no device"""
+    buf = C.create_string_buffer(1 << 14)
+    n = lib.fa_measure_candidates_text(ptype, rank, flags, buf, len(buf))
+    return buf.value.decode().splitlines()[:n]
 
 
 def elem_form(step, src_mis, dst_mis, cn):

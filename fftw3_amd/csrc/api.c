@@ -104,6 +104,58 @@ static int fa_is_planes_plan(const plan *q) {
            s[1].kind == FFTW_AMD_STEP_PASS && s[1].src_buf == 1 && s[1].dst_buf == 1;
 }
 
+/* the first family that c has on, NULL: none (a MEASURE candidate has at most one) */
+static const fa_family *fa_family_of(const fa_cfg *c) {
+    int i;
+    for (i = 0; i < FA_NFAMILIES; ++i) if (fa_family_on(c, &fa_family_table[i])) return &fa_family_table[i];
+    return NULL;
+}
+
+/* is q, built with family f on, the plan the family stands for (fa_family.accept)?  If not, its emitter declined and q
+   is a plan that the base candidates already cover */
+static int fa_family_accepts(const fa_family *f, const plan *q) {
+    if (f->accept == FA_ACCEPT_ANY) return 1;
+    if (f->accept == FA_ACCEPT_PLANES) return fa_is_planes_plan(q);
+    return q->nsteps == 1 && q->steps[0].variant == f->accept;
+}
+
+/* base with the six fields the FFTW_MEASURE search varies set from the indices of its loops */
+static fa_cfg measure_cfg(fa_cfg base, int ci, int pi, int li, int st, int lf) {
+    static const size_t chunks[5] = { (size_t)64 << 20, (size_t)128 << 20, (size_t)256 << 20, (size_t)1 << 30,
+                                      (size_t)4 << 30 };
+    base.chunk_bytes = chunks[ci];
+    base.pipeline = pi;
+    base.lanes = pi ? 1 : (ci < 3 ? 2 : 1);   /* small chunks: two chunk lanes; large ones: serial or the stage pipeline */
+    base.lmax_multi = li ? 512 : 1024;
+    base.small_tiles = st;
+    base.long_first = lf;
+    return base;
+}
+
+/* The configurations the FFTW_MEASURE search times for a problem of `type` and `rank`, in the order it times them,
+   into out[0 .. cap); returns how many.  First the base candidates, every family off whatever `base` says; the second
+   value of lmax_multi and of small_tiles only under FFTW_PATIENT / FFTW_EXHAUSTIVE, so plain MEASURE never tries
+   small_tiles = 1, the ESTIMATE default.  Then one candidate per row of fa_family_table whose types and rank fit: the
+   base candidate with 128 MiB chunks and that family alone on.  tile_elems stays what it is in `base`. */
+#define FA_MEASURE_CAP (80 + FA_NFAMILIES)
+static int fa_measure_candidates(int type, int rank, unsigned flags, fa_cfg base, fa_cfg *out, int cap) {
+    const int nl = (flags & (FFTW_PATIENT | FFTW_EXHAUSTIVE)) ? 2 : 1;
+    int ci, pi, li, st, lf, i, n = 0;
+    for (i = 0; i < FA_NFAMILIES; ++i) fa_family_set(&base, &fa_family_table[i], 0);
+    for (ci = 0; ci < 5; ++ci)
+        for (pi = 0; pi < 2; ++pi)
+            for (li = 0; li < nl; ++li)
+                for (st = 0; st < nl; ++st)
+                    for (lf = 0; lf < 2 && n < cap; ++lf) out[n++] = measure_cfg(base, ci, pi, li, st, lf);
+    for (i = 0; i < FA_NFAMILIES && n < cap; ++i) {
+        const fa_family *f = &fa_family_table[i];
+        if (!(f->types & (1u << type)) || (f->rank && f->rank != rank)) continue;
+        out[n] = measure_cfg(base, 1, 0, 0, 0, 0);
+        fa_family_set(&out[n++], f, 1);
+    }
+    return n;
+}
+
 /* copy the problem description of `p` into a fresh plan with configuration c */
 static plan *clone_problem(const plan *p, fa_cfg c) {
     plan *q = fa_plan_new();
@@ -192,66 +244,31 @@ static plan *finish_locked(plan *p, double *ri, double *ii, double *ro, double *
             return NULL;
         } else if (!(p->flags & FFTW_ESTIMATE) && ri && ro && fa_hip_device_count() > 0) {
             /* FFTW_MEASURE / PATIENT / EXHAUSTIVE: time candidate configurations on the device */
-            static const size_t chunks[] = { (size_t)64 << 20, (size_t)128 << 20, (size_t)256 << 20, (size_t)1 << 30, (size_t)4 << 30 };
-            fa_cfg best = p->cfg, c;
+            fa_cfg cand[FA_MEASURE_CAP], best = p->cfg;
             double best_ms = -1.0;
-            int ci, pi, li, st, lf, rd, nl = (p->flags & (FFTW_PATIENT | FFTW_EXHAUSTIVE)) ? 2 : 1;
-            /* r2c and c2r problems: also the two-trip plan decimated over the real data (cfg.real_dec, rd = 1) and the one-trip
-               plan of small real images (cfg.real_img, rd = 2), each with the default chunking only; those of rank 3 also the
-               one-trip plan of small real volumes (cfg.real_vol, rd = 3), those of rank 2 the one-trip plan of real images with an
-               extent above 32 (cfg.real_imgl, rd = 3), both skipped when the plan is not the single step; c2c problems of rank 3
-               likewise the one-trip plan of small volumes (cfg.vol3d, rd = 1), skipped when its plan lacks the step, and the
-               two-trip planes plan (cfg.vol_planes, rd = 2), skipped when its plan is not the image step and one pass; c2c
-               problems of rank 2 the one-trip plan of images with an extent of 128 (cfg.img_wide, rd = 1), skipped when its
-               plan is not the single step */
-            const int real = (p->type == FA_R2C || p->type == FA_C2R);
-            const int nrd = real ? ((p->rank == 3 || p->rank == 2) ? 4 : 3) : ((p->type == FA_C2C && p->rank == 3) ? 3 : ((p->type == FA_C2C && p->rank == 2) ? 2 : 1));
-            for (rd = 0; rd < nrd; ++rd)
-            for (ci = 0; ci < 5; ++ci)
-                for (pi = 0; pi < 2; ++pi)
-                    for (li = 0; li < nl; ++li)
-                        for (st = 0; st < nl; ++st)
-                        for (lf = 0; lf < 2; ++lf) {
-                            if (rd && (ci != 1 || pi || li || st || lf)) continue;
-                            plan *q;
-                            double t0, dt;
-                            c = p->cfg;
-                            c.chunk_bytes = chunks[ci];
-                            c.pipeline = pi;
-                            c.lanes = pi ? 1 : (ci < 3 ? 2 : 1);   /* small chunks: two chunk lanes; large ones: serial or the stage pipeline */
-                            c.lmax_multi = li ? 512 : 1024;
-                            c.small_tiles = st;
-                            c.long_first = lf;
-                            c.real_dec = real && rd == 1;
-                            c.real_img = real && rd == 2;
-                            c.vol3d = !real && p->rank == 3 && rd == 1;
-                            c.vol_planes = !real && p->rank == 3 && rd == 2;
-                            c.img_wide = !real && p->rank == 2 && rd == 1;
-                            c.real_vol = real && p->rank == 3 && rd == 3;
-                            c.real_imgl = real && p->rank == 2 && rd == 3;
-                            q = clone_problem(p, c);
-                            if (!q) continue;
-                            /* the builder looks at the arrays (alignment, aliasing) */
-                            q->ri = ri; q->ii = ii; q->ro = ro; q->io = io;
-                            q->inplace = p->inplace;
-                            if (fa_build(q)) { fa_plan_free(q); continue; }
-                            if (c.vol3d && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3D)) { fa_plan_free(q); continue; }
-                            if (c.vol_planes && !fa_is_planes_plan(q)) { fa_plan_free(q); continue; }
-                            if (c.img_wide && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_IMG2DW)) { fa_plan_free(q); continue; }
-                            if (c.real_vol && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_VOL3DR)) { fa_plan_free(q); continue; }
-                            if (c.real_imgl && !(q->nsteps == 1 && q->steps[0].variant == FFTW_AMD_K_IMG2DLR)) { fa_plan_free(q); continue; }
-                            q->in_lo = p->in_lo; q->in_hi = p->in_hi; q->out_lo = p->out_lo; q->out_hi = p->out_hi;
-                            q->out_written = p->out_written;
-                            fa_run(q, ri, ii, ro, io);          /* warm-up, device init */
-                            fa_hip_stream_sync(q->stream);
-                            t0 = now_ms();
-                            fa_run(q, ri, ii, ro, io);
-                            fa_run(q, ri, ii, ro, io);
-                            fa_hip_stream_sync(q->stream);
-                            dt = 0.5 * (now_ms() - t0);
-                            if (best_ms < 0 || dt < best_ms) { best_ms = dt; best = c; }
-                            fa_plan_free(q);
-                        }
+            const int ncand = fa_measure_candidates(p->type, p->rank, p->flags, p->cfg, cand, FA_MEASURE_CAP);
+            int k;
+            for (k = 0; k < ncand; ++k) {
+                const fa_family *f = fa_family_of(&cand[k]);
+                plan *q = clone_problem(p, cand[k]);
+                double t0, dt;
+                if (!q) continue;
+                /* the builder looks at the arrays (alignment, aliasing) */
+                q->ri = ri; q->ii = ii; q->ro = ro; q->io = io;
+                q->inplace = p->inplace;
+                if (fa_build(q) || (f && !fa_family_accepts(f, q))) { fa_plan_free(q); continue; }
+                q->in_lo = p->in_lo; q->in_hi = p->in_hi; q->out_lo = p->out_lo; q->out_hi = p->out_hi;
+                q->out_written = p->out_written;
+                fa_run(q, ri, ii, ro, io);          /* warm-up, device init */
+                fa_hip_stream_sync(q->stream);
+                t0 = now_ms();
+                fa_run(q, ri, ii, ro, io);
+                fa_run(q, ri, ii, ro, io);
+                fa_hip_stream_sync(q->stream);
+                dt = 0.5 * (now_ms() - t0);
+                if (best_ms < 0 || dt < best_ms) { best_ms = dt; best = cand[k]; }   /* the first of equal times wins */
+                fa_plan_free(q);
+            }
             p->cfg = best;
             wis_put(key, best, best_ms);
         }
@@ -824,8 +841,35 @@ void fftw_cleanup_threads(void) {}
 void fftw_make_planner_thread_safe(void) {}
 
 /* ---- wisdom: text records "(key) chunk pipeline lmax bits ms", one per problem
-   (bits: 1 = small_tiles, 2 = long_first, 4 | 8 = chunk lanes - 1, 16 = real_dec, 32 = real_img, 64 = vol3d,
-   128 = real_vol, 256 = real_imgl, 512 = vol_planes, 1024 = img_wide) */
+   (bits: 1 = small_tiles, 2 = long_first, 4 | 8 = chunk lanes - 1, from 16 up the plan families: fa_family_table) */
+static int cfg_to_bits(const fa_cfg *c) {
+    int bits = (c->small_tiles ? 1 : 0) | (c->long_first ? 2 : 0) | (((c->lanes > 1 ? c->lanes - 1 : 0) & 3) << 2), i;
+    for (i = 0; i < FA_NFAMILIES; ++i) if (fa_family_on(c, &fa_family_table[i])) bits |= fa_family_table[i].bit;
+    return bits;
+}
+static void cfg_from_bits(fa_cfg *c, int bits) {
+    int i;
+    c->small_tiles = (bits & 1) != 0;
+    c->long_first = (bits & 2) != 0;
+    c->lanes = 1 + ((bits >> 2) & 3);
+    for (i = 0; i < FA_NFAMILIES; ++i) fa_family_set(c, &fa_family_table[i], (bits & fa_family_table[i].bit) != 0);
+}
+
+/* the candidates of fa_measure_candidates under the default configuration, one line "chunk pipeline lmax bits" each --
+   the four integers of a wisdom record; returns how many.  For the tests: needs no device */
+int fa_measure_candidates_text(int type, int rank, unsigned flags, char *buf, size_t cap) {
+    fa_cfg cand[FA_MEASURE_CAP];
+    const int n = fa_measure_candidates(type, rank, flags, fa_default_cfg(), cand, FA_MEASURE_CAP);
+    size_t len = 0;
+    int k;
+    if (cap) buf[0] = 0;
+    for (k = 0; k < n; ++k) {
+        const fa_cfg *c = &cand[k];
+        kapp(buf, cap, &len, "%zu %d %d %d\n", c->chunk_bytes, c->pipeline, c->lmax_multi, cfg_to_bits(c));
+    }
+    return n;
+}
+
 void fftw_forget_wisdom(void) {
     pthread_mutex_lock(&g_planner_lock);
     while (g_wisdom) { wis_entry *n = g_wisdom->next; free(g_wisdom); g_wisdom = n; }
@@ -844,7 +888,7 @@ char *fftw_export_wisdom_to_string(void) {
     len += (size_t)snprintf(s + len, cap - len, "(fftw3_amd_wisdom-1\n");
     for (w = g_wisdom; w; w = w->next)
         len += (size_t)snprintf(s + len, cap - len, "  (%s) %zu %d %d %d %.6f\n", w->key, w->cfg.chunk_bytes,
-                                w->cfg.pipeline, w->cfg.lmax_multi, (w->cfg.small_tiles ? 1 : 0) | (w->cfg.long_first ? 2 : 0) | (((w->cfg.lanes > 1 ? w->cfg.lanes - 1 : 0) & 3) << 2) | (w->cfg.real_dec ? 16 : 0) | (w->cfg.real_img ? 32 : 0) | (w->cfg.vol3d ? 64 : 0) | (w->cfg.real_vol ? 128 : 0) | (w->cfg.real_imgl ? 256 : 0) | (w->cfg.vol_planes ? 512 : 0) | (w->cfg.img_wide ? 1024 : 0), w->ms);
+                                w->cfg.pipeline, w->cfg.lmax_multi, cfg_to_bits(&w->cfg), w->ms);
     snprintf(s + len, cap - len, ")\n");
     pthread_mutex_unlock(&g_planner_lock);
     return s;
@@ -876,7 +920,7 @@ int fftw_import_wisdom_from_string(const char *input) {
     for (;;) {
         char key[FA_WIS_KEY_CAP];
         size_t chunk;
-        int pipe, lmax, small, n = 0;
+        int pipe, lmax, bits, n = 0;
         double ms;
         const char *o, *e;
         while (*c == ' ' || *c == '\n' || *c == '\t' || *c == '\r') ++c;
@@ -887,12 +931,15 @@ int fftw_import_wisdom_from_string(const char *input) {
         if (!e || (size_t)(e - o) >= sizeof(key)) { ok = 0; break; }
         memcpy(key, o, (size_t)(e - o));
         key[e - o] = 0;
-        if (sscanf(e + 1, " %zu %d %d %d %lf%n", &chunk, &pipe, &lmax, &small, &ms, &n) != 5) { ok = 0; break; }
+        if (sscanf(e + 1, " %zu %d %d %d %lf%n", &chunk, &pipe, &lmax, &bits, &ms, &n) != 5) { ok = 0; break; }
         if (chunk < ((size_t)1 << 16) || lmax < 16 || lmax > 1024) { ok = 0; break; }
         w = (wis_entry *)calloc(1, sizeof(*w));
         if (!w) { ok = 0; break; }
         snprintf(w->key, sizeof(w->key), "%s", key);
-        w->cfg.chunk_bytes = chunk; w->cfg.pipeline = pipe != 0; w->cfg.lmax_multi = lmax; w->cfg.small_tiles = (small & 1) != 0; w->cfg.long_first = (small & 2) != 0; w->cfg.lanes = 1 + ((small >> 2) & 3); w->cfg.real_dec = (small & 16) != 0; w->cfg.real_img = (small & 32) != 0; w->cfg.vol3d = (small & 64) != 0; w->cfg.real_vol = (small & 128) != 0; w->cfg.real_imgl = (small & 256) != 0; w->cfg.vol_planes = (small & 512) != 0; w->cfg.img_wide = (small & 1024) != 0;
+        w->cfg.chunk_bytes = chunk;
+        w->cfg.pipeline = pipe != 0;
+        w->cfg.lmax_multi = lmax;
+        cfg_from_bits(&w->cfg, bits);
         w->ms = ms;
         w->next = staged;
         staged = w;

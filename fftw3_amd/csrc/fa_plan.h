@@ -65,27 +65,35 @@ typedef struct {
     int long_first;       /* multi-pass splits run the longest sub-transform first */
     int lanes;            /* chunk lanes: chunk c runs all its steps on stream c % lanes, scratch slot c % lanes */
     i64 tile_elems;       /* FFTW_AMD_TILE_ELEMS: tile size of the generic LDS kernel, 0 = default (not tuned) */
-    int real_dec;         /* FFTW_AMD_REAL_DEC: long r2c transforms decimated over the real data (two trips on the 512-item
-                             kernels, emit_r2c_decimated) instead of the half- / quarter-length plans; off by default
-                             (measured a few % behind them except near n = 2^20), a FFTW_MEASURE candidate */
-    int real_img;         /* FFTW_AMD_REAL_IMG: batches of small 2-D r2c / c2r transforms in one trip (emit_real_image,
-                             FFTW_AMD_K_IMG2DR) instead of the three-trip plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
-                             candidate */
-    int vol3d;            /* FFTW_AMD_VOL3D: batches of small 3-D c2c transforms in one trip (emit_vol3d, FFTW_AMD_K_VOL3D)
-                             instead of one trip per axis; off under FFTW_ESTIMATE, a FFTW_MEASURE candidate */
-    int real_vol;         /* FFTW_AMD_REAL_VOL: batches of small 3-D r2c / c2r transforms in one trip (emit_real_volume,
-                             FFTW_AMD_K_VOL3DR) instead of the axis-by-axis plans; off under FFTW_ESTIMATE, a FFTW_MEASURE
-                             candidate; a knob of its own, not implied by real_img */
-    int real_imgl;        /* FFTW_AMD_REAL_IMGL: batches of 2-D r2c / c2r transforms with extents up to 64, at least one above
-                             32, in one trip (emit_real_image, FFTW_AMD_K_IMG2DLR) instead of the axis-by-axis plans; off
-                             under FFTW_ESTIMATE, a FFTW_MEASURE candidate; a knob of its own, not implied by real_img */
-    int vol_planes;       /* FFTW_AMD_VOL_PLANES: dense 3-D c2c volumes in two trips, the (n1, n2) planes as one image step and
-                             the first axis as one pass in place on the output (emit_vol_planes), instead of one trip per
-                             axis; off under FFTW_ESTIMATE, a FFTW_MEASURE candidate */
-    int img_wide;         /* FFTW_AMD_IMG_WIDE: batches of 2-D c2c transforms 128 x 128, 64 x 128 and 128 x 64 in one trip
-                             (emit_images, FFTW_AMD_K_IMG2DW) instead of the two-trip plans; off under FFTW_ESTIMATE, a
-                             FFTW_MEASURE candidate.  Not needed for the planes of a vol_planes plan */
+    /* the opt-in plan families: 0 under FFTW_ESTIMATE; what switches each on, and for which problems, is its row of
+       fa_family_table below */
+    int real_dec;         /* long r2c / c2r transforms decimated over the real data, two trips */
+    int real_img;         /* batches of small 2-D r2c / c2r transforms in one trip */
+    int vol3d;            /* batches of small 3-D c2c transforms in one trip */
+    int real_vol;         /* batches of small 3-D r2c / c2r transforms in one trip; not implied by real_img */
+    int real_imgl;        /* batches of 2-D r2c / c2r transforms with an extent above 32 in one trip; nor is this one */
+    int vol_planes;       /* dense 3-D c2c volumes in two trips: the (n1, n2) planes, then the first axis */
+    int img_wide;         /* batches of 2-D c2c transforms with an extent of 128 in one trip; not needed by vol_planes */
 } fa_cfg;
+
+/* One row per opt-in plan family, and the only place that says what switches it on: the environment variable
+   (fa_default_cfg: the field is atoi(value) != 0 when the variable is present), the bit of a wisdom record's flag
+   integer, and the problems for which the FFTW_MEASURE search times one candidate with that field alone set -- after
+   its base candidates, in the order of the rows (api.c: fa_measure_candidates) -- and which plan it then accepts. */
+enum { FA_ACCEPT_ANY = -1, FA_ACCEPT_PLANES = -2 };
+typedef struct {
+    const char *env;
+    size_t off;         /* of the int field in fa_cfg */
+    int bit;            /* of the wisdom record */
+    unsigned types;     /* problem types the search tries it for: 1 << FA_C2C | ... */
+    int rank;           /* the rank it tries it for, 0 = every rank */
+    int accept;         /* the candidate is timed when its plan is: FA_ACCEPT_ANY any plan that builds, FA_ACCEPT_PLANES
+                           the two steps of emit_vol_planes, otherwise exactly one step of this FFTW_AMD_K_* variant */
+} fa_family;
+#define FA_NFAMILIES 7
+__attribute__((visibility("hidden"))) extern const fa_family fa_family_table[FA_NFAMILIES];
+static inline int fa_family_on(const fa_cfg *c, const fa_family *f) { return *(const int *)((const char *)c + f->off); }
+static inline void fa_family_set(fa_cfg *c, const fa_family *f, int on) { *(int *)((char *)c + f->off) = on; }
 
 /* The planner's test switches, read from the environment by fa_read_knobs at the top of every fa_build (planner.c)
    and from nowhere else: one build -- its dry run and its sized runs -- sees one snapshot.  Not part of fa_cfg:

@@ -51,9 +51,26 @@ void fftw_amd_set_chunk_bytes(size_t nbytes) {
 static i64 iabs(i64 v) { return v < 0 ? -v : v; }
 static int is_pow2(i64 n) { return (n & (n - 1)) == 0; }
 
+/* The opt-in plan families (fa_plan.h), in the order the FFTW_MEASURE search tries them.  Why each is off under
+   FFTW_ESTIMATE, what it takes and what was measured is said once, at its emitter: emit_r2c_decimated and
+   emit_c2r_decimated, emit_real_image (real_img and real_imgl), emit_real_volume, emit_vol3d, emit_vol_planes,
+   emit_images (img_wide). */
+#define T_REAL (1u << FA_R2C | 1u << FA_C2R)
+#define T_C2C  (1u << FA_C2C)
+const fa_family fa_family_table[FA_NFAMILIES] = {
+    { "FFTW_AMD_REAL_DEC",   offsetof(fa_cfg, real_dec),     16, T_REAL, 0, FA_ACCEPT_ANY },
+    { "FFTW_AMD_REAL_IMG",   offsetof(fa_cfg, real_img),     32, T_REAL, 0, FA_ACCEPT_ANY },
+    { "FFTW_AMD_REAL_VOL",   offsetof(fa_cfg, real_vol),    128, T_REAL, 3, FFTW_AMD_K_VOL3DR },
+    { "FFTW_AMD_REAL_IMGL",  offsetof(fa_cfg, real_imgl),   256, T_REAL, 2, FFTW_AMD_K_IMG2DLR },
+    { "FFTW_AMD_VOL3D",      offsetof(fa_cfg, vol3d),        64, T_C2C,  3, FFTW_AMD_K_VOL3D },
+    { "FFTW_AMD_VOL_PLANES", offsetof(fa_cfg, vol_planes),  512, T_C2C,  3, FA_ACCEPT_PLANES },
+    { "FFTW_AMD_IMG_WIDE",   offsetof(fa_cfg, img_wide),   1024, T_C2C,  2, FFTW_AMD_K_IMG2DW },
+};
+
 fa_cfg fa_default_cfg(void) {
     fa_cfg c;
     const char *e;
+    int i;
     c.chunk_bytes = __atomic_load_n(&g_chunk_bytes, __ATOMIC_RELAXED);
     c.pipeline = 0;       /* two-stream chunk pipeline: off under FFTW_ESTIMATE (each kernel then owns the machine and
                              its launch duration is its roofline), a FFTW_MEASURE candidate, FFTW_AMD_PIPELINE=1 */
@@ -61,13 +78,6 @@ fa_cfg fa_default_cfg(void) {
     c.small_tiles = 1;
     c.long_first = 0;
     c.tile_elems = 0;
-    c.real_dec = 0;
-    c.real_img = 0;
-    c.vol3d = 0;
-    c.real_vol = 0;
-    c.real_imgl = 0;
-    c.vol_planes = 0;
-    c.img_wide = 0;
     c.lanes = 2;
     e = getenv("FFTW_AMD_CHUNK_BYTES");
     if (e && atoll(e) > 0) c.chunk_bytes = (size_t)atoll(e);
@@ -81,22 +91,12 @@ fa_cfg fa_default_cfg(void) {
     if (e) c.pipeline = atoi(e);
     e = getenv("FFTW_AMD_LMAX_MULTI");
     if (e && atoll(e) >= 16) c.lmax_multi = (int)atoll(e);
-    e = getenv("FFTW_AMD_REAL_DEC");
-    if (e) c.real_dec = atoi(e) != 0;
-    e = getenv("FFTW_AMD_REAL_IMG");
-    if (e) c.real_img = atoi(e) != 0;
-    e = getenv("FFTW_AMD_VOL3D");
-    if (e) c.vol3d = atoi(e) != 0;
-    e = getenv("FFTW_AMD_REAL_VOL");
-    if (e) c.real_vol = atoi(e) != 0;
-    e = getenv("FFTW_AMD_REAL_IMGL");
-    if (e) c.real_imgl = atoi(e) != 0;
-    e = getenv("FFTW_AMD_VOL_PLANES");
-    if (e) c.vol_planes = atoi(e) != 0;
-    e = getenv("FFTW_AMD_IMG_WIDE");
-    if (e) c.img_wide = atoi(e) != 0;
     e = getenv("FFTW_AMD_LANES");
     if (e && atoi(e) >= 1 && atoi(e) <= FA_MAXLANES) c.lanes = atoi(e);
+    for (i = 0; i < FA_NFAMILIES; ++i) {
+        e = getenv(fa_family_table[i].env);
+        fa_family_set(&c, &fa_family_table[i], e && atoi(e) != 0);
+    }
     return c;
 }
 
